@@ -12,10 +12,17 @@ One step = one align() (NanoGICP::computeTransformation), index build and
 covariances excluded (SURVEY.md §8(d) "ms/scan").  value = outer GICP
 iterations per second over the whole job (all ranks); ms_per_step = ms/scan.
 
+A plain run sets the problem up, warms up, times --steps aligns, writes the
+last align's pose and result to --dump-outputs DIR (when given) and prints
+the result line.  The inputs are seeded, so they are identical from run to
+run.  Everything below the headline (the roofline, the comparisons with the
+candidate cells off and with varied guesses, the CPU baseline and the other
+configurations' legs) runs only with --full.
+
 Multi-GPU (torchrun, one process per GPU): the headline runs an independent
 replica per GPU (weak scaling, no data-path collective); torch.distributed is
 used for the barrier and max-time / sum-work only.  Extra legs in the same
-JSON line: s2s_gn (cfg 2, 20 fixed GN iterations), sharded_s2m (cfg 4,
+JSON line with --full: s2s_gn (cfg 2, 20 fixed GN iterations), sharded_s2m (cfg 4,
 spatial shards + one RCCL all-reduce per iteration), batched_s2s (cfg 5
 frame-parallel S2S) and odometry (cfg 5 S2M chain through the ddlo_odom
 driver, one independent chain per rank's frame segment).
@@ -201,6 +208,21 @@ def rot_err(A, B):
     """Rotation angle between A and B: 2*asin(|RA - RB|_F / sqrt(8)) (well conditioned at 0)."""
     f = float(np.linalg.norm(A[:3, :3].astype(np.float64) - B[:3, :3].astype(np.float64)))
     return 2.0 * math.asin(min(1.0, f / math.sqrt(8.0)))
+
+
+def dump_outputs(dirname, out, res):
+    """--dump-outputs: what the last timed align() handed its caller, one .npy per array.  pose is the
+    final transformation (4x4 float32); final_hessian the 6x6 float64 normal matrix; result the
+    deterministic scalar fields of the result struct as float64, in RESULT_FIELDS order (the device
+    timings and tie-resolver counters of the struct are measurements, not results)."""
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "pose.npy"), np.asarray(out, np.float32).reshape(4, 4))
+    np.save(os.path.join(dirname, "final_hessian.npy"), np.array(res.final_hessian, np.float64).reshape(6, 6))
+    np.save(os.path.join(dirname, "result.npy"), np.array([getattr(res, f) for f in RESULT_FIELDS], np.float64))
+
+
+RESULT_FIELDS = ("converged", "nr_iterations", "iterations_run", "lm_failed", "lm_trials", "num_correspondences",
+                 "final_cost", "lm_lambda")
 
 
 def sharded_leg(dist, rank, world, local_rank, args):
@@ -580,6 +602,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed align returned to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the roofline, the walk and varied-guess comparisons, the CPU "
+                         "baseline and the cfg 2 / 4 / 5 and segmentation legs (the --no-* options prune them); "
+                         "without it only the headline is set up, timed and printed")
     ap.add_argument("--cpu-runs", type=int, default=10, help="oracle align runs for cpu_baseline (median)")
     ap.add_argument("--cpu-warmup", type=int, default=2, help="untimed oracle aligns before them")
     ap.add_argument("--no-cpu", action="store_true")
@@ -638,7 +666,7 @@ def main():
     # the per-target build (once per setInputTarget; like the index, outside ms/scan): the first align
     ctx.synchronize()
     t_b = time.perf_counter()
-    ctx.align(guess)
+    out, res = ctx.align(guess)
     first_align_ms = 1e3 * (time.perf_counter() - t_b)
     grid_info = ctx.grid_info()
 
@@ -662,20 +690,8 @@ def main():
     steps_total = args.steps * world
     value = iters_total / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
-
-    # roofline: linearize launches timed with HIP events on the library stream
-    ctx.set_profiling(True)
-    lin_ms, lin_launches = 0.0, 0
-    for _ in range(max(3, min(args.steps, 10))):
-        _, r = ctx.align(guess)
-        lin_ms += r.linearize_ms
-        lin_launches += r.iterations_run
-    ctx.set_profiling(False)
-    ctx.synchronize()
-    avg_launch_s = (lin_ms / max(lin_launches, 1)) * 1e-3
-    bytes_per_launch = 76.0 * len(src)   # SURVEY.md §8(d) B_lin = 76 * N_s
-    traffic, traffic_src = pmc_traffic()
-    achieved_gbs = bytes_per_launch / avg_launch_s / 1e9 if avg_launch_s > 0 else 0.0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, res)
 
     result = {
         "metric": METRIC,
@@ -695,19 +711,47 @@ def main():
                    "source_points": int(len(src)), "target_points": int(len(sub)),
                    "iterations_per_scan": round(iters_total / steps_total, 3),
                    "parallelism": f"replicas x{world}"},
-        "roofline": {"bound": "hbm", "achieved": round(achieved_gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved_gbs / HBM_PEAK_GBS, 6), "traffic": traffic,
-                     "traffic_unit": "bytes per linearize launch (L2->fabric, Infinity-Cache hits included; counters as read)",
-                     "traffic_source": traffic_src,
-                     "kernel": lin_kernel_label(ctx),
-                     "avg_launch_us": round(avg_launch_s * 1e6, 2),
-                     "algorithmic_bytes_per_launch": int(bytes_per_launch)},
     }
-
     result["target_grid"] = {**grid_info, "first_align_ms": round(first_align_ms, 3),
                              "walk_groups_last_align": ctx.lookup_walk_groups(),
                              "note": "candidate cells of the submap, built once per target (first align, outside "
                                      "ms/scan like the index build, SURVEY.md §8(d)); the odometry leg pays them"}
+    if args.full:
+        full_legs(dist, rank, world, local_rank, args, result, ctx, prob, sub, src, scov, tcov, params, guess, out,
+                  ms_per_step)
+    ctx.close()
+    if rank == 0:
+        print(json.dumps(result), file=json_out, flush=True)
+    if dist:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_legs(dist, rank, world, local_rank, args, result, ctx, prob, sub, src, scov, tcov, params, guess, out,
+              ms_per_step):
+    """--full: everything the benchmark measures beside the headline, added to `result` (the headline's
+    ctx is closed before the legs that make their own)."""
+    # roofline: linearize launches timed with HIP events on the library stream
+    ctx.set_profiling(True)
+    lin_ms, lin_launches = 0.0, 0
+    for _ in range(max(3, min(args.steps, 10))):
+        _, r = ctx.align(guess)
+        lin_ms += r.linearize_ms
+        lin_launches += r.iterations_run
+    ctx.set_profiling(False)
+    ctx.synchronize()
+    avg_launch_s = (lin_ms / max(lin_launches, 1)) * 1e-3
+    bytes_per_launch = 76.0 * len(src)   # SURVEY.md §8(d) B_lin = 76 * N_s
+    traffic, traffic_src = pmc_traffic()
+    achieved_gbs = bytes_per_launch / avg_launch_s / 1e9 if avg_launch_s > 0 else 0.0
+    result["roofline"] = {"bound": "hbm", "achieved": round(achieved_gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                          "frac": round(achieved_gbs / HBM_PEAK_GBS, 6), "traffic": traffic,
+                          "traffic_unit": "bytes per linearize launch (L2->fabric, Infinity-Cache hits included; counters as read)",
+                          "traffic_source": traffic_src,
+                          "kernel": lin_kernel_label(ctx),
+                          "avg_launch_us": round(avg_launch_s * 1e6, 2),
+                          "algorithmic_bytes_per_launch": int(bytes_per_launch)}
+
     # the same aligns with the cells off (the round-4 walk), for comparison
     if not args.no_walk:
         cfg3_walk_leg(ctx, guess, args, result)
@@ -799,11 +843,6 @@ def main():
         result["odometry"] = odometry_leg(dist, rank, world, local_rank, args)
     if not args.no_seg:
         result["segmentation"] = segmentation_leg(local_rank, args)
-    if rank == 0:
-        print(json.dumps(result), file=json_out, flush=True)
-    if dist:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

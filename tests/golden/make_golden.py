@@ -16,8 +16,11 @@ container, where /root/reference exists; the GPU box only reads the .npz).
                   unpinned" for the reference's GICP arithmetic).
   gicp_s2m.npz    oracle S2M problem: 16x512 scan -> 12,000-pt submap of 3
                   keyframes (per-keyframe k=10 covariances, subset), LM align.
+  ref_digests.json  SHA-256 digests of the reference nanoflann's kd-trees and
+                  kNN answers on the seeded clouds of tests/test_nftree_cpu.py
+                  and tests/test_oracle.py (tests/ref_digest.py).
 
-usage: make oracle && python tests/golden/make_golden.py
+usage: make oracle && python tests/golden/make_golden.py [digests]
 """
 import os
 import sys
@@ -115,10 +118,37 @@ def s2m_fixture():
                         cost=np.float64(res.final_cost), trace=g.trace())
 
 
+def digest_fixture():
+    """ref_digests.json: digests of the reference nanoflann's trees on tests/test_nftree_cpu.py's clouds and
+    of its kNN answers on tests/test_oracle.py's random problem (the data is seeded; its digest is kept too)."""
+    import json
+    sys.path.insert(0, os.path.dirname(HERE))
+    import ref_digest as D
+    from test_nftree_cpu import _clouds
+    assert O.ref_lib() is not None, "oracle/_ref/libref_nanoflann.so missing: build it with `make oracle` here"
+    out = {"trees": {}, "knn_random": {}}
+    for name, pts in sorted(_clouds().items()):
+        out["trees"][name] = {"points": D.arrays_digest(pts), "tree": D.tree_digest(O.ref_tree(pts))}
+    rng = np.random.default_rng(3)
+    pts = (rng.standard_normal((5000, 3)) * [10, 10, 2]).astype(np.float32)
+    q = (rng.standard_normal((700, 3)) * [12, 12, 3]).astype(np.float32)
+    out["knn_random"]["inputs"] = D.arrays_digest(pts, q)
+    for k in (1, 7, 20):
+        i, d = O.ref_knn(pts, q, k)
+        out["knn_random"][f"k{k}"] = D.arrays_digest(i, d)
+    with open(D.PATH, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["digests"]:   # only ref_digests.json (the .npz files stay as they are)
+        digest_fixture()
+        sys.exit(0)
     knn_fixture()
     s2s_fixture()
     s2m_fixture()
+    digest_fixture()
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(HERE, f)))

@@ -3,8 +3,9 @@ the structure that fixes the reference's order among exactly equidistant
 points (DESIGN.md "Tie order").
 
 * The oracle's tree restatement (oracle/cpu_ref.cpp) is pinned to the
-  reference's own nanoflann compiled from /root/reference (oracle/_ref):
-  identical vind permutation, leaves and divfeat / divlow / divhigh.
+  reference's own nanoflann: identical vind permutation, leaves and
+  divfeat / divlow / divhigh as its recorded trees (tests/golden/ref_digests.json)
+  and, where the reference build (oracle/_ref) is present, as its trees built now.
 * planeSplit's two Hoare loops (reference impl/nanoflann_impl.hpp:1107-1143)
   equal the rank pairing the device uses to run them in parallel: with
   L = #{good}, the r-th bad element of [0, L) (ascending) swaps with the r-th
@@ -12,6 +13,7 @@ points (DESIGN.md "Tie order").
 import numpy as np
 import pytest
 
+import ref_digest as D
 from oracle import oracle as O
 
 
@@ -96,8 +98,14 @@ def _clouds():
 
 @pytest.mark.parametrize("name", sorted(_clouds()))
 def test_oracle_tree_is_reference_tree(name):
+    """Against the reference's tree as recorded (tests/golden/ref_digests.json) and, where oracle/_ref
+    is built, against the reference's tree built now."""
     pts = _clouds()[name]
+    gold = D.load()["trees"][name]
+    assert D.arrays_digest(pts) == gold["points"], "the test cloud changed: regenerate tests/golden/ref_digests.json"
+    mine = O.tree(pts)
     ref = O.ref_tree(pts)
-    if ref is None:
-        pytest.skip("reference nanoflann (oracle/_ref) not built here")
-    assert O.same_tree(O.tree(pts), ref) is None
+    if ref is not None:
+        assert O.same_tree(mine, ref) is None
+        assert D.tree_digest(ref) == gold["tree"]
+    assert D.tree_digest(mine) == gold["tree"]

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import np_gicp as NP
+import ref_digest as D
 from oracle import oracle as O
 
 
@@ -34,17 +35,21 @@ def test_oracle_knn_edge_goldens(knn_golden, case):
 
 
 def test_oracle_knn_live_vs_reference_build():
-    """When oracle/_ref was built here (dev container), compare on fresh random data too."""
-    if O.ref_lib() is None:
-        pytest.skip("oracle/_ref not built (reference absent)")
+    """Random data too: against the reference's answers as recorded (tests/golden/ref_digests.json) and,
+    where oracle/_ref is built, against the reference build run now."""
     rng = np.random.default_rng(3)
     pts = (rng.standard_normal((5000, 3)) * [10, 10, 2]).astype(np.float32)
     q = (rng.standard_normal((700, 3)) * [12, 12, 3]).astype(np.float32)
+    gold = D.load()["knn_random"]
+    assert D.arrays_digest(pts, q) == gold["inputs"], "the test data changed: regenerate tests/golden/ref_digests.json"
     for k in (1, 7, 20):
         a = O.knn(pts, q, k)
-        b = O.ref_knn(pts, q, k)
-        np.testing.assert_array_equal(a[0], b[0])
-        np.testing.assert_array_equal(a[1], b[1])
+        if O.ref_lib() is not None:
+            b = O.ref_knn(pts, q, k)
+            np.testing.assert_array_equal(a[0], b[0])
+            np.testing.assert_array_equal(a[1], b[1])
+            assert D.arrays_digest(b[0], b[1]) == gold[f"k{k}"]
+        assert D.arrays_digest(a[0], a[1]) == gold[f"k{k}"]
 
 
 def test_knn_golden_distances_are_true_minima(knn_golden):

@@ -5,7 +5,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r06
 mkdir -p $O
-HEAD="--no-cpu --no-sharded --no-batch --no-odom --no-gn --no-seg --no-walk"
+HEAD="--full --no-cpu --no-sharded --no-batch --no-odom --no-gn --no-seg --no-walk"
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 150 rocprofv3 --pmc $c --output-format csv -d $O/pmc_$c -o run -- python3 bench.py $HEAD --steps 5 --warmup 1 > $O/pmc_$c.log 2>&1 || { echo "PMC pass $c failed"; tail -5 $O/pmc_$c.log; exit 1; }
 done
@@ -28,7 +28,7 @@ for leg in cfg2 cfg4 cfg5; do
   rm -rf $O/pmc_${leg}_FETCH_SIZE $O/pmc_${leg}_WRITE_SIZE
   echo "$leg done"
 done
-DDLO_TRAFFIC_JSON=$O/traffic.json timeout -k 10 900 python -u bench.py > $O/bench.json 2> $O/bench.err || { echo BENCH_FAIL; tail -20 $O/bench.err; exit 1; }
+DDLO_TRAFFIC_JSON=$O/traffic.json timeout -k 10 900 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { echo BENCH_FAIL; tail -20 $O/bench.err; exit 1; }
 cat $O/bench.json | cut -c1-600
 timeout -k 10 600 python -u tools/slab_cells_table.py 2 4 8 > $O/slab_cells_table.log 2>&1 || { echo SLAB_FAIL; tail -20 $O/slab_cells_table.log; exit 1; }
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || exit 1
