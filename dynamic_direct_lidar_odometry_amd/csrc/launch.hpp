@@ -111,19 +111,26 @@ void launch_cov_remap(hipStream_t s, const double* old_cov6, const int* old_inv_
 // preprocess.hip (odometry driver): see the kernels there for the reference
 // filters they restate.  Scratch sizes: *_tmp_bytes (hipcub temporaries).
 void launch_pack4(hipStream_t s, const unsigned char* raw, size_t stride, int n, float4* out);
+// centre of the crop box (CropBox::setTranslation); the origin by default
+struct CropCentre {
+  float x = 0.f, y = 0.f, z = 0.f;
+};
 // pin: pinned host ints for the count read-back (crop_box 2, voxel_grid 16)
+// box = false: no box, only the non-finite points are dropped
 int crop_box(hipStream_t s, const float4* in, int n, float size, float4* out, int* keep, int* pos, void* tmp,
-             size_t tmp_bytes, int* count_host, int* pin);
+             size_t tmp_bytes, int* count_host, int* pin, CropCentre centre = CropCentre(), bool box = true);
 size_t crop_box_tmp_bytes(int n);
 // crop > 0: the crop box (points inside [-crop, crop]^3 removed) folded into the same pass
 int voxel_grid(hipStream_t s, const float4* in, int n, float leaf, float4* out, int* scratch, void* tmp, size_t tmp_bytes,
-               int* count_host, float crop, int* pin);
+               int* count_host, float crop, int* pin, CropCentre centre = CropCentre());
 size_t voxel_tmp_bytes(int n);
 constexpr size_t voxel_scratch_ints(int n) { return 7 * (size_t)n + 16 + 6 * 64; }
 void median_range_async(hipStream_t s, const float4* in, int n, float* d, float* result, void* tmp, size_t tmp_bytes,
                         float* out);
 size_t median_tmp_bytes(int n);
 void launch_transform4(hipStream_t s, const float4* pts, const int* perm, int n, const float* T12, float4* out);
+// organized raw scan -> world frame float4, pixel order kept (non-finite pixels: NaN)
+void launch_transform_raw(hipStream_t s, const unsigned char* raw, size_t stride, int n, const float* T12, float4* out);
 void launch_gather_cov6(hipStream_t s, const double* cov_sorted, const int* perm, int n, double* out);
 
 }  // namespace ddlo

@@ -13,6 +13,10 @@
 //   scanMatching          :745-851   S2S, propagateS2S, cov reuse, swap,
 //                                    getSubmapKeyframes, S2M, propagateS2M
 //   transformScans        :941-947   device transform to the world frame
+//   applySegmentation     :853-918   process_dynamic: world-frame scan (device),
+//                                    residual image, segmentation, objects, the
+//                                    caller's verdict; a new keyframe's cloud
+//                                    is the scan without the non-static objects
 //   updateKeyframes       :1067-1154 keyframe decision; the keyframe cloud
 //                                    (submap voxel filter) and its k-NN
 //                                    covariances stay on the device
@@ -46,6 +50,7 @@
 #include "launch.hpp"
 #include "runtime.hpp"
 #include "devknobs.hpp"
+#include "seg_internal.hpp"
 
 namespace {
 
@@ -488,6 +493,21 @@ struct ddlo_odom {
   float median_prev = 0.f;
   double thresh_dist = 1.0;
   int64_t submap_points = 0;
+  // process_dynamic: the residual image, the frame's objects and the segments to cut out
+  float* resid_pin = nullptr;   // pinned, resid_cap pixels
+  size_t resid_cap = 0;
+  std::vector<ddlo_seg_object> dyn_objs;
+  std::vector<uint8_t> dyn_flags;
+  std::vector<int32_t> dyn_remove;
+};
+
+// the dynamic-object step's arguments (ddlo_odom_process_dynamic)
+struct DynStep {
+  ddlo_seg* seg;
+  ddlo_dynamic_params dp;
+  ddlo_nonstatic_fn decide;
+  void* user;
+  ddlo_seg_result* seg_res;
 };
 
 namespace {
@@ -559,17 +579,14 @@ gicp_status cloud_from(ddlo_odom* o, gicp_ctx* c, const float4* pts, int n, std:
   return build_cloud(c, reinterpret_cast<const float*>(pts), (size_t)n, sizeof(float4), out, true, !finite, with_cov);
 }
 
-// keyframe = world-frame copy of the (preprocessed) scan cloud, submap voxel
-// filter, k-NN covariances with the S2S parameters (odom.cc:1129-1149)
-gicp_status make_keyframe(ddlo_odom* o, const std::shared_ptr<CloudData>& scan) {
+// keyframe from the n world-frame points in o->a: submap voxel filter, k-NN
+// covariances with the S2S parameters (odom.cc:1133-1149)
+gicp_status make_keyframe_from_a(ddlo_odom* o, int n) {
   auto kf = std::make_unique<Keyframe>();
   kf->pose[0] = o->pose[0];
   kf->pose[1] = o->pose[1];
   kf->pose[2] = o->pose[2];
   kf->q = o->rotq;
-  const int n = scan->n;
-  HIP_TRY(o->a.ensure(sizeof(float4) * (size_t)n));
-  launch_transform4(o->s, scan->pts.as<float4>(), scan->perm.as<int>(), n, o->T, o->a.as<float4>());
   int m = n;
   gicp_status st = preprocess(o, n, false, 0.0, o->p.vf_submap_use != 0, o->p.vf_submap_res, &m);
   if (st) return st;
@@ -592,6 +609,75 @@ gicp_status make_keyframe(ddlo_odom* o, const std::shared_ptr<CloudData>& scan) 
   st = check_ties(o->s2s);   // the keyframe's (and the first scan's) covariance tie resolution
   if (st) return st;
   o->keyframes.push_back(std::move(kf));
+  return GICP_OK;
+}
+
+// keyframe = world-frame copy of the (preprocessed) scan cloud (odom.cc:1129-1131)
+gicp_status make_keyframe(ddlo_odom* o, const std::shared_ptr<CloudData>& scan) {
+  const int n = scan->n;
+  HIP_TRY(o->a.ensure(sizeof(float4) * (size_t)n));
+  launch_transform4(o->s, scan->pts.as<float4>(), scan->perm.as<int>(), n, o->T, o->a.as<float4>());
+  return make_keyframe_from_a(o, n);
+}
+
+// keyframe = the segmented scan without its non-static objects
+// (applySegmentation, odom.cc:887-918: segmentation_scan_t_ is what
+// updateKeyframes stores), cropped around pose_ and voxel-filtered
+gicp_status make_keyframe_static(ddlo_odom* o, const DynStep& d) {
+  const float4* pts = nullptr;
+  int n = 0;
+  gicp_status st = seg_static_cloud_dev(d.seg, o->dyn_remove.data(), o->dyn_remove.size(), o->pose,
+                                        o->p.crop_use ? o->p.crop_size : 0.0, o->p.vf_scan_use ? o->p.vf_scan_res : 0.0,
+                                        &pts, &n);
+  if (st) return st;
+  if (n < 1) return fail(GICP_ETOOFEW, "keyframe without points");
+  // (o->a is free: metrics() has waited for the median kernel, its last reader)
+  HIP_TRY(o->a.ensure(sizeof(float4) * (size_t)n));
+  HIP_TRY(hipMemcpyAsync(o->a.p, pts, sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, o->s));
+  return make_keyframe_from_a(o, n);
+}
+
+// OdomNode::applySegmentation up to the tracker's verdict (odom.cc:853-870),
+// on a tracked frame after propagateS2M: o->up still holds the frame's
+// organized scan (npix points, stride bytes apart)
+gicp_status dynamic_step(ddlo_odom* o, const DynStep& d, int npix, size_t stride) {
+  float4* buf = nullptr;
+  int n = 0;
+  gicp_status st = seg_stage_input(d.seg, &buf, &n);
+  if (st) return st;
+  if (n != npix) return fail(GICP_EINVAL, "scan size != the segmentation's rows x cols");
+  launch_transform_raw(o->s, o->up.as<unsigned char>(), stride, npix, o->T, buf);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(o->s));
+  ddlo_seg_params sp;
+  st = seg_get_params(d.seg, &sp);
+  if (st) return st;
+  if (o->resid_cap < (size_t)npix) {
+    if (o->resid_pin) (void)hipHostFree(o->resid_pin);
+    o->resid_pin = nullptr;
+    o->resid_cap = 0;
+    HIP_TRY(hipHostMalloc((void**)&o->resid_pin, sizeof(float) * (size_t)npix, hipHostMallocDefault));
+    o->resid_cap = (size_t)npix;
+  }
+  st = gicp_residual_image(o->s2m, d.dp.theta_min, d.dp.theta_max, sp.cols, sp.rows, o->resid_pin, nullptr);
+  if (st) return st;
+  ddlo_seg_result sr{};
+  st = seg_process_staged(d.seg, o->T, o->resid_pin, &sr);
+  if (st) return st;
+  if (d.seg_res) *d.seg_res = sr;
+  st = seg_objects_vec(d.seg, d.dp.max_dim_ratio, o->dyn_objs);
+  if (st) return st;
+  const size_t k = o->dyn_objs.size();
+  o->dyn_flags.assign(k + 1, 0);
+  if (d.decide) {
+    if (d.decide(d.user, o->dyn_objs.data(), k, o->dyn_flags.data()) != 0)
+      return fail(GICP_ESTATE, "the non-static callback aborted the scan");
+  } else {
+    std::fill(o->dyn_flags.begin(), o->dyn_flags.end(), (uint8_t)1);
+  }
+  o->dyn_remove.clear();
+  for (size_t i = 0; i < k; ++i)
+    if (o->dyn_flags[i]) o->dyn_remove.push_back(o->dyn_objs[i].id);
   return GICP_OK;
 }
 
@@ -761,6 +847,7 @@ gicp_status ddlo_odom_destroy(ddlo_odom* o) {
   }
   o->keyframes.clear();
   if (o->median_pin) (void)hipHostFree(o->median_pin);
+  if (o->resid_pin) (void)hipHostFree(o->resid_pin);
   if (o->med_in) (void)hipEventDestroy(o->med_in);
   if (o->med_done) (void)hipEventDestroy(o->med_done);
   gicp_ctx_destroy(o->s2m);
@@ -769,7 +856,9 @@ gicp_status ddlo_odom_destroy(ddlo_odom* o) {
   return GICP_OK;
 }
 
-gicp_status ddlo_odom_process(ddlo_odom* o, const float* xyz, size_t n, size_t stride, ddlo_odom_result* res) {
+// OdomNode::icpCB; dyn: the dynamic-object step of ddlo_odom_process_dynamic (else nullptr)
+static gicp_status process_scan(ddlo_odom* o, const float* xyz, size_t n, size_t stride, ddlo_odom_result* res,
+                                const DynStep* dyn) {
   if (!o || !res || (!xyz && n) || stride < 12 || stride % 4) return fail(GICP_EINVAL, "invalid argument");
   if (n > (size_t)INT32_MAX / 2) return fail(GICP_EINVAL, "scan too large");
   gicp_status st = set_device(o->s2s);
@@ -919,6 +1008,10 @@ gicp_status ddlo_odom_process(ddlo_odom* o, const float* xyz, size_t n, size_t s
   o->pose[1] = o->T[7];
   o->pose[2] = o->T[11];
   o->rotq = quat_from_R(o->T);
+  if (dyn) {
+    st = dynamic_step(o, *dyn, N, stride);
+    if (st) return st;
+  }
 
   // updateKeyframes (odom.cc:1067-1154)
   {
@@ -945,7 +1038,8 @@ gicp_status ddlo_odom_process(ddlo_odom* o, const float* xyz, size_t n, size_t s
     if (std::fabs(dd) <= o->thresh_dist) add = false;
     if (std::fabs(dd) <= o->thresh_dist && std::fabs(theta_deg) > o->p.keyframe_thresh_rot && num_nearby <= 1) add = true;
     if (add) {
-      st = make_keyframe(o, scan);   // registration_scan_t_ = T_ * scan (transformScans)
+      // registration_scan_t_ = T_ * scan (transformScans), or the segmented scan without its non-static objects
+      st = dyn ? make_keyframe_static(o, *dyn) : make_keyframe(o, scan);
       if (st) return st;
       res->keyframe_added = 1;
     }
@@ -962,6 +1056,51 @@ gicp_status ddlo_odom_process(ddlo_odom* o, const float* xyz, size_t n, size_t s
   res->num_keyframes = (int)o->keyframes.size();
   res->submap_keyframes = (int)o->submap_prev.size();
   res->submap_points = o->submap_points;
+  return GICP_OK;
+}
+
+gicp_status ddlo_odom_process(ddlo_odom* o, const float* xyz, size_t n, size_t stride, ddlo_odom_result* res) {
+  return process_scan(o, xyz, n, stride, res, nullptr);
+}
+
+gicp_status ddlo_dynamic_default_params(ddlo_dynamic_params* p) {
+  if (!p) return fail(GICP_EINVAL, "null params");
+  p->theta_min = -60 * M_PI / 180;   // odom.cc:804-805
+  p->theta_max = 60 * M_PI / 180;
+  p->max_dim_ratio = 10.0f;          // detection.cpp:106
+  return GICP_OK;
+}
+
+gicp_status ddlo_odom_process_dynamic(ddlo_odom* o, ddlo_seg* seg, const float* xyz, size_t stride,
+                                      const ddlo_dynamic_params* dp, ddlo_nonstatic_fn decide, void* user,
+                                      ddlo_odom_result* res, ddlo_seg_result* seg_res) {
+  if (!o || !seg || !xyz || !res) return fail(GICP_EINVAL, "null argument");
+  if (seg_device(seg) != o->device) return fail(GICP_EINVAL, "the segmentation lives on another device");
+  ddlo_seg_params sp;
+  gicp_status st = seg_get_params(seg, &sp);
+  if (st) return st;
+  DynStep d{seg, {}, decide, user, seg_res};
+  if (dp) d.dp = *dp;
+  else ddlo_dynamic_default_params(&d.dp);
+  if (!(d.dp.theta_max > d.dp.theta_min)) return fail(GICP_EINVAL, "theta_max must exceed theta_min");
+  if (seg_res) std::memset(seg_res, 0, sizeof(*seg_res));
+  return process_scan(o, xyz, (size_t)sp.rows * sp.cols, stride, res, &d);
+}
+
+gicp_status ddlo_odom_keyframe_points(const ddlo_odom* o, int k, float* xyz, size_t cap, size_t* n) {
+  if (!o || !n || (!xyz && cap) || k < 0 || k >= (int)o->keyframes.size()) return fail(GICP_EINVAL, "invalid argument");
+  const Keyframe& kf = *o->keyframes[k];
+  *n = (size_t)kf.n;
+  const size_t m = std::min(cap, (size_t)kf.n);
+  if (m == 0) return GICP_OK;
+  HIP_TRY(hipSetDevice(o->device));
+  std::vector<float4> h(m);
+  HIP_TRY(hipMemcpy(h.data(), kf.pts.p, sizeof(float4) * m, hipMemcpyDeviceToHost));   // (idle: process waited for it)
+  for (size_t i = 0; i < m; ++i) {
+    xyz[3 * i] = h[i].x;
+    xyz[3 * i + 1] = h[i].y;
+    xyz[3 * i + 2] = h[i].z;
+  }
   return GICP_OK;
 }
 

@@ -41,14 +41,19 @@ __global__ __launch_bounds__(256) void k_pack4(const unsigned char* __restrict__
 }
 
 // ---- crop box (negative: keep the points strictly outside [-s, s]^3) ----
-__global__ __launch_bounds__(256) void k_crop_flags(const float4* __restrict__ in, int n, float s, int* __restrict__ keep) {
+// c: the box's translation (CropBox::setTranslation: the point is moved by
+// -c, in float, before the test; the origin leaves it as it is).  box == 0:
+// no box, only the finite test.
+__global__ __launch_bounds__(256) void k_crop_flags(const float4* __restrict__ in, int n, float s, CropCentre c, int box,
+                                                    int* __restrict__ keep) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float4 p = in[i];
   // CropBox::applyFilter: non-finite points are dropped; a point with any
   // coordinate below min or above max is outside the box (kept when negative)
   const bool finite = isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
-  const bool outside = p.x < -s || p.y < -s || p.z < -s || p.x > s || p.y > s || p.z > s;
+  const float x = p.x - c.x, y = p.y - c.y, z = p.z - c.z;
+  const bool outside = !box || x < -s || y < -s || z < -s || x > s || y > s || z > s;
   keep[i] = finite && outside ? 1 : 0;
 }
 
@@ -62,18 +67,19 @@ __global__ __launch_bounds__(256) void k_compact(const float4* __restrict__ in, 
 // ---- voxel grid --------------------------------------------------------------
 // The points a voxel pass sees: finite, and — when the crop box is folded
 // into the pass (crop > 0) — outside [-crop, crop]^3 (k_crop_flags' rule).
-__device__ __forceinline__ bool voxel_input(float4 p, float crop) {
+__device__ __forceinline__ bool voxel_input(float4 p, float crop, CropCentre c) {
   if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z))) return false;
-  return !(crop > 0.f) || (p.x < -crop || p.y < -crop || p.z < -crop || p.x > crop || p.y > crop || p.z > crop);
+  const float x = p.x - c.x, y = p.y - c.y, z = p.z - c.z;
+  return !(crop > 0.f) || (x < -crop || y < -crop || z < -crop || x > crop || y > crop || z > crop);
 }
 
 // bbox of those points: per-block partial min/max, then one block
 __global__ __launch_bounds__(256) void k_minmax_partial(const float4* __restrict__ in, int n, float crop,
-                                                        float* __restrict__ part) {
+                                                        CropCentre cc, float* __restrict__ part) {
   float v[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const float4 p = in[i];
-    if (!voxel_input(p, crop)) continue;
+    if (!voxel_input(p, crop, cc)) continue;
     v[0] = fminf(v[0], p.x); v[1] = fminf(v[1], p.y); v[2] = fminf(v[2], p.z);
     v[3] = fmaxf(v[3], p.x); v[4] = fmaxf(v[4], p.y); v[5] = fmaxf(v[5], p.z);
   }
@@ -125,7 +131,8 @@ __device__ void voxel_geometry(const float* __restrict__ part, float inv_x, floa
 // Voxel index of every point (non-finite or cropped points get UINT_MAX and
 // sort last, they are dropped by the caller's count).
 __global__ __launch_bounds__(256) void k_voxel_keys(const float4* __restrict__ in, int n, float inv_x, float inv_y,
-                                                    float inv_z, float crop, const float* __restrict__ part,
+                                                    float inv_z, float crop, CropCentre cc,
+                                                    const float* __restrict__ part,
                                                     int* __restrict__ small, unsigned* __restrict__ key,
                                                     int* __restrict__ idx) {
   __shared__ float sp[kVoxParts * 6];
@@ -145,7 +152,7 @@ __global__ __launch_bounds__(256) void k_voxel_keys(const float4* __restrict__ i
   if (i >= n) return;
   const float4 p = in[i];
   unsigned k = 0xffffffffu;
-  if (voxel_input(p, crop)) {   // (no such point when geo[6]: the geometry is not read)
+  if (voxel_input(p, crop, cc)) {   // (no such point when geo[6]: the geometry is not read)
     const int i0 = (int)(floorf(p.x * inv_x) - (float)geo[0]);
     const int i1 = (int)(floorf(p.y * inv_y) - (float)geo[1]);
     const int i2 = (int)(floorf(p.z * inv_z) - (float)geo[2]);
@@ -214,6 +221,22 @@ __global__ __launch_bounds__(256) void k_transform4(const float4* __restrict__ p
                              (m[8] * p.x + m[9] * p.y) + (m[10] * p.z + m[11]), 0.f);
 }
 
+// an organized sensor-frame scan (strided host layout) to the world frame, in
+// place order: out[i] = T * p(i) with k_transform4's operation order; a
+// non-finite point stays non-finite in every coordinate (0 * inf, NaN + x)
+__global__ __launch_bounds__(256) void k_transform_raw(const unsigned char* __restrict__ raw, size_t stride, int n, T34 T,
+                                                       float4* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* p = reinterpret_cast<const float*>(raw + (size_t)i * stride);
+  const float x = p[0], y = p[1], z = p[2];
+  const float* m = T.m;
+  float4 r = make_float4((m[0] * x + m[1] * y) + (m[2] * z + m[3]), (m[4] * x + m[5] * y) + (m[6] * z + m[7]),
+                         (m[8] * x + m[9] * y) + (m[10] * z + m[11]), 0.f);
+  if (!(isfinite(x) && isfinite(y) && isfinite(z))) r = make_float4(NAN, NAN, NAN, 0.f);
+  out[i] = r;
+}
+
 // covariances of a cloud (sym6 per SORTED point) back to original order
 __global__ __launch_bounds__(256) void k_gather_cov6(const double* __restrict__ cov_sorted, const int* __restrict__ perm,
                                                      int n, double* __restrict__ out) {
@@ -227,12 +250,12 @@ __global__ __launch_bounds__(256) void k_gather_cov6(const double* __restrict__ 
 // host launchers
 // ============================================================================
 int crop_box(hipStream_t s, const float4* in, int n, float size, float4* out, int* keep, int* pos, void* tmp,
-             size_t tmp_bytes, int* count_host, int* pin) {
+             size_t tmp_bytes, int* count_host, int* pin, CropCentre centre, bool box) {
   if (n <= 0) {
     *count_host = 0;
     return 0;
   }
-  k_crop_flags<<<cdiv_l(n, 256), 256, 0, s>>>(in, n, size, keep);
+  k_crop_flags<<<cdiv_l(n, 256), 256, 0, s>>>(in, n, size, centre, box ? 1 : 0, keep);
   size_t need = 0;
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, need, keep, pos, n, s);
   if (need > tmp_bytes) return -1;
@@ -267,7 +290,7 @@ size_t voxel_tmp_bytes(int n) {
 // pin: 16 ints of pinned host memory (the read-back of small).  small needs
 // no clearing: every slot the host reads ([5], [6], [8], [9]) is written.
 int voxel_grid(hipStream_t s, const float4* in, int n, float leaf, float4* out, int* scratch, void* tmp, size_t tmp_bytes,
-               int* count_host, float crop, int* pin) {
+               int* count_host, float crop, int* pin, CropCentre centre) {
   *count_host = 0;
   if (n <= 0) return 0;
   unsigned* keys = reinterpret_cast<unsigned*>(scratch);
@@ -281,8 +304,8 @@ int voxel_grid(hipStream_t s, const float4* in, int n, float leaf, float4* out, 
   float* part = reinterpret_cast<float*>(small + 16);
   // inverse_leaf_size_ = 1 / leaf_size_ (float)
   const float inv = 1.0f / leaf;
-  k_minmax_partial<<<kVoxParts, 256, 0, s>>>(in, n, crop, part);
-  k_voxel_keys<<<cdiv_l(n, 256), 256, 0, s>>>(in, n, inv, inv, inv, crop, part, small, keys, idx);
+  k_minmax_partial<<<kVoxParts, 256, 0, s>>>(in, n, crop, centre, part);
+  k_voxel_keys<<<cdiv_l(n, 256), 256, 0, s>>>(in, n, inv, inv, inv, crop, centre, part, small, keys, idx);
   size_t need = voxel_tmp_bytes(n);
   if (need > tmp_bytes) return -2;
   size_t t = tmp_bytes;
@@ -442,6 +465,11 @@ void launch_transform4(hipStream_t s, const float4* pts, const int* perm, int n,
   T34 T;
   for (int e = 0; e < 12; ++e) T.m[e] = T12[e];
   k_transform4<<<cdiv_l(n, 256), 256, 0, s>>>(pts, perm, n, T, out);
+}
+void launch_transform_raw(hipStream_t s, const unsigned char* raw, size_t stride, int n, const float* T12, float4* out) {
+  T34 T;
+  for (int e = 0; e < 12; ++e) T.m[e] = T12[e];
+  k_transform_raw<<<cdiv_l(n, 256), 256, 0, s>>>(raw, stride, n, T, out);
 }
 void launch_gather_cov6(hipStream_t s, const double* cov_sorted, const int* perm, int n, double* out) {
   k_gather_cov6<<<cdiv_l(n, 256), 256, 0, s>>>(cov_sorted, perm, n, out);

@@ -37,6 +37,7 @@
 #include "gicp_types.hpp"
 #include "launch.hpp"
 #include "runtime.hpp"
+#include "seg_internal.hpp"
 
 namespace ddlo {
 namespace {
@@ -57,6 +58,7 @@ struct SegPixelArgs {
   float* range;
   signed char* ground;
   int* label;
+  float* zout;           // cloud_in_t z of every pixel (a scan staged on the device), or nullptr
 };
 
 // full_cloud_ point of pixel i (:309-327): the cloud point when finite with
@@ -111,6 +113,7 @@ __global__ __launch_bounds__(256) void k_seg_pixels(SegPixelArgs a) {
     if (ground_test(lo, me, a.mount, a.thr) == 1) g = 1;
   }
   a.range[i] = r;
+  if (a.zout) a.zout[i] = reinterpret_cast<const float*>(a.raw + (size_t)i * a.stride)[2];
   a.ground[i] = g;
   a.label[i] = (g == 1 || r == 0.f) ? DDLO_SEG_EXCLUDED : DDLO_SEG_UNLABELLED;
 }
@@ -122,6 +125,9 @@ inline int cdiv_s(long a, long b) { return (int)((a + b - 1) / b); }
 struct LabelWork {
   std::vector<int> qy, qx, py, px, rows_hit;
   std::vector<char> line_flag;   // all zero between components
+  // the feasible segments' pixels in the order the labelling pushed them, as CSR:
+  // seg_pix[seg_off[l] .. seg_off[l + 1]) for l = 1 .. segments (seg_off[0] = seg_off[1] = 0)
+  std::vector<int> seg_off, seg_pix;
 };
 
 // cloudSegmentation + labelComponents (detection.cpp:510-724) over host images.
@@ -147,11 +153,13 @@ struct Labeller {
   std::vector<int>& px;
   std::vector<int>& rows_hit;
   std::vector<char>& line_flag;
+  std::vector<int>& seg_off;
+  std::vector<int>& seg_pix;
 
   Labeller(const ddlo_seg_params& p_, const float* range_, const float* z_, const float* resid_, int* label_,
            float sensor_z_, std::vector<double>& avg, LabelWork& w)
       : p(p_), range(range_), z(z_), resid(resid_), label(label_), sensor_z(sensor_z_), avg_residual(avg), qy(w.qy),
-        qx(w.qx), py(w.py), px(w.px), rows_hit(w.rows_hit), line_flag(w.line_flag) {
+        qx(w.qx), py(w.py), px(w.px), rows_hit(w.rows_hit), line_flag(w.line_flag), seg_off(w.seg_off), seg_pix(w.seg_pix) {
     const int H = p.rows, W = p.cols;
     // loadParams :82-83,108-111: ang_res_x_ = 360.0 / float(W_) (double, stored
     // as float), ang_res_y_ = 2 * ang_bottom_ / float(H_ - 1) (float); double sin/cos
@@ -178,6 +186,8 @@ struct Labeller {
     rows_hit.clear();
     rows_hit.reserve(H);
     avg_residual.assign(1, 0.0);
+    seg_off.assign(2, 0);
+    seg_pix.clear();
   }
 
   bool in_window(int r, int c) const { return r >= p.win_row0 && r <= p.win_row1 && c >= p.win_col0 && c <= p.win_col1; }
@@ -267,6 +277,8 @@ struct Labeller {
     if (feasible) feasible = min_z - sensor_z <= p.max_elevation;
     if (feasible) {
       avg_residual.push_back(avg);   // avg_residuals_[label_count_]
+      for (int i = 0; i < pushed; ++i) seg_pix.push_back(py[i] * W + px[i]);
+      seg_off.push_back((int)seg_pix.size());
       ++label_count;
     } else {
       for (int i = 0; i < pushed; ++i) label[(size_t)py[i] * W + px[i]] = kRejected;
@@ -281,6 +293,233 @@ gicp_status check_params(const ddlo_seg_params* p) {
   return GICP_OK;
 }
 
+// ---- objects: one oriented bounding box per segment (getObject, detection.cpp:726-782) ----
+// One workgroup per segment, over the segment's pixel list (the labelling
+// records it; ddlo_seg_objects_from derives it from the label image), three
+// times:
+//   1. sum x, sum y, min / max z                   -> the centroid
+//   2. the centred 2 x 2 covariance of (x, y)      -> the principal axes, in
+//      closed form (every lane computes the same values from the same sums)
+//   3. min / max of the points projected on them   -> centre and dimensions
+// Sums are doubles reduced in a fixed order: each thread adds its pixels in
+// list order (thread t takes entries t, t + 1024, ...), the wavefront folds by
+// shuffles, the sixteen wavefront sums are added 0..15 from LDS.  No atomics:
+// the result does not depend on the grid or on timing, only on the list's
+// order.  The kernel is bound by the latency of its dependent loads (list
+// entry, then point), so the workgroup is as wide as it can be: a 6000-point
+// segment is six rounds per pass.  (Measured on a 512 x 512 frame's ten
+// segments: 37 us with 256 threads; 194 us for a first version that walked
+// the segment's rows of the label image instead of a list.)
+constexpr int kObjThreads = 1024;
+
+struct SegObjArgs {
+  const unsigned char* raw;
+  size_t stride;
+  const int* off;         // CSR: segment l's pixels are pix[off[l] .. off[l + 1])
+  const int* pix;         // row-major pixel indices
+  ddlo_seg_object* out;   // [l - 1]
+};
+
+struct OpSum {
+  __device__ static double f(double a, double b) { return a + b; }
+};
+struct OpMax {
+  __device__ static double f(double a, double b) { return fmax(a, b); }
+};
+
+// v[k] <- the block's reduction of v[k], in every thread
+template <class Op, int K>
+__device__ __forceinline__ void block_reduce(double (&v)[K], double (*sh)[kObjThreads / 64]) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v[k] = Op::f(v[k], __shfl_down(v[k], d, 64));
+  __syncthreads();   // the previous reduction's readers are done with sh
+  if (lane == 0)
+#pragma unroll
+    for (int k = 0; k < K; ++k) sh[k][w] = v[k];
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    double r = sh[k][0];
+#pragma unroll
+    for (int j = 1; j < kObjThreads / 64; ++j) r = Op::f(r, sh[k][j]);
+    v[k] = r;
+  }
+}
+
+__global__ __launch_bounds__(kObjThreads) void k_seg_objects(SegObjArgs a) {
+  __shared__ double sh[4][kObjThreads / 64];
+  const int l = blockIdx.x + 1;
+  ddlo_seg_object* const out = a.out + blockIdx.x;
+  const int first = a.off[l], last = a.off[l + 1];   // (first == last: no pixel, the loops do not run)
+  auto point = [&](int i) { return reinterpret_cast<const float*>(a.raw + (size_t)a.pix[i] * a.stride); };
+  // 1. centroid, z range (float min / max are exact in any order)
+  const int cnt = last - first;
+  if (cnt == 0) {   // (uniform)
+    if (threadIdx.x == 0) {
+      out->id = l;
+      out->num_points = 0;
+    }
+    return;
+  }
+  double s1[2] = {0.0, 0.0};             // sum x, sum y
+  double zr[2] = {-INFINITY, -INFINITY}; // max z, max -z
+  for (int i = first + (int)threadIdx.x; i < last; i += kObjThreads) {
+    const float* p = point(i);
+    s1[0] += (double)p[0];
+    s1[1] += (double)p[1];
+    zr[0] = fmax(zr[0], (double)p[2]);
+    zr[1] = fmax(zr[1], -(double)p[2]);
+  }
+  block_reduce<OpSum>(s1, sh);
+  block_reduce<OpMax>(zr, sh);
+  const double cx = s1[0] / (double)cnt, cy = s1[1] / (double)cnt;
+  // 2. centred covariance (its scale does not matter to the axes)
+  double s2[3] = {0.0, 0.0, 0.0};
+  for (int i = first + (int)threadIdx.x; i < last; i += kObjThreads) {
+    const float* p = point(i);
+    const double dx = (double)p[0] - cx, dy = (double)p[1] - cy;
+    s2[0] += dx * dx;
+    s2[1] += dx * dy;
+    s2[2] += dy * dy;
+  }
+  block_reduce<OpSum>(s2, sh);
+  // symmetric 2 x 2 [[cxx, cxy], [cxy, cyy]]: the major axis is (d + h, 2 cxy)
+  // for d = cxx - cyy >= 0, (2 cxy, h - d) otherwise, h = hypot(d, 2 cxy); the
+  // minor axis is its normal.  h == 0: equal eigenvalues, axis (1, 0).
+  double ax = 1.0, ay = 0.0;
+  {
+    const double d = s2[0] - s2[2], b2 = 2.0 * s2[1];
+    const double h = sqrt(d * d + b2 * b2);
+    if (h > 0.0) {
+      const double mx = d >= 0.0 ? d + h : b2, my = d >= 0.0 ? b2 : h - d;
+      const double nrm = sqrt(mx * mx + my * my);
+      ax = -my / nrm;
+      ay = mx / nrm;
+      if (ax < 0.0 || (ax == 0.0 && ay < 0.0)) {
+        ax = -ax;
+        ay = -ay;
+      }
+    }
+  }
+  // 3. extent along the axes (axis, then (-axis.y, axis.x)), about the centroid
+  double e[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};   // max u, max -u, max v, max -v
+  for (int i = first + (int)threadIdx.x; i < last; i += kObjThreads) {
+    const float* p = point(i);
+    const double dx = (double)p[0] - cx, dy = (double)p[1] - cy;
+    const double u = ax * dx + ay * dy, v = ax * dy - ay * dx;
+    e[0] = fmax(e[0], u);
+    e[1] = fmax(e[1], -u);
+    e[2] = fmax(e[2], v);
+    e[3] = fmax(e[3], -v);
+  }
+  block_reduce<OpMax>(e, sh);
+  if (threadIdx.x != 0) return;
+  const double umax = e[0], umin = -e[1], vmax = e[2], vmin = -e[3];
+  const double mu = 0.5 * (umax + umin), mv = 0.5 * (vmax + vmin);
+  const double du = umax - umin, dv = vmax - vmin;
+  const float zmax = (float)zr[0], zmin = (float)-zr[1];
+  const float dz = zmax - zmin;
+  out->id = l;
+  out->num_points = cnt;
+  out->state[0] = (float)((ax * mu - ay * mv) + cx);   // eigen_vectors_PCA * mean_XY + centroid
+  out->state[1] = (float)((ay * mu + ax * mv) + cy);
+  out->state[2] = 0.5f * (zmax + zmin);
+  // sin(atan2(ay, ax) / 2) with ax >= 0: sin(t / 2) = sin t / sqrt(2 (1 + cos t))
+  out->state[3] = (float)(ay / sqrt(2.0 * (1.0 + ax)));
+  out->state[4] = (float)du;
+  out->state[5] = (float)dv;
+  out->state[6] = dz;
+  out->axis[0] = (float)ax;
+  out->axis[1] = (float)ay;
+  out->density = (float)((double)cnt / ((du * dv) * (double)dz));
+  out->avg_residuum = 0.0;   // the host fills it in
+}
+
+// the pixels of the removed segments made NaN in the packed scan: the crop
+// box / voxel pass drops non-finite points, so the removal, the finite test
+// and the crop are one keep predicate there
+__global__ __launch_bounds__(256) void k_static_drop(const int* __restrict__ pix, int m, float4* __restrict__ pts) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < m) pts[pix[j]] = make_float4(NAN, NAN, NAN, 0.f);
+}
+
+// computeAllObjects' ratio test (:800-804) and avg_residuals_ on the kernel's records
+void filter_objects(const std::vector<ddlo_seg_object>& recs, const double* avg, size_t avg_n, float max_dim_ratio,
+                    std::vector<ddlo_seg_object>& out) {
+  out.clear();
+  for (const ddlo_seg_object& r : recs) {
+    if (r.num_points <= 0) continue;
+    double d[3] = {r.state[4], r.state[5], r.state[6]};
+    std::sort(d, d + 3);
+    if (d[2] / d[1] >= max_dim_ratio) continue;
+    ddlo_seg_object o = r;
+    o.avg_residuum = (avg && (size_t)r.id < avg_n) ? avg[r.id] : 0.0;
+    out.push_back(o);
+  }
+}
+
+// pinned staging of the object kernel's small transfers (the segments' rows
+// in, the records out), grown on demand: pageable copies of a few hundred
+// bytes each cost more than the kernel
+struct ObjStage {
+  void* p = nullptr;
+  size_t bytes = 0;
+  gicp_status ensure(size_t b) {
+    if (b <= bytes) return GICP_OK;
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    bytes = 0;
+    const size_t want = std::max<size_t>(2 * b, 4096);
+    HIP_TRY(hipHostMalloc(&p, want, hipHostMallocDefault));
+    bytes = want;
+    return GICP_OK;
+  }
+  void release() {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+};
+
+// launch the object kernel for labels 1 .. L and read the records back
+// (stage: pinned staging, or nullptr for pageable copies)
+// off: L + 2 offsets, pix: off[L + 1] pixel indices (CSR, as ddlo_seg_label_indices)
+gicp_status run_objects(hipStream_t s, const unsigned char* raw, size_t stride, const std::vector<int>& off,
+                        const std::vector<int>& pix, int L, DevBuf& dcsr, DevBuf& dobj,
+                        std::vector<ddlo_seg_object>& recs, ObjStage* stage) {
+  recs.assign((size_t)L, ddlo_seg_object{});
+  if (L <= 0) return GICP_OK;
+  const size_t noff = (size_t)L + 2, npix = (size_t)off[L + 1];
+  const size_t rows_b = sizeof(int) * (noff + npix), rec_b = sizeof(ddlo_seg_object) * (size_t)L;
+  const size_t rec_off = (rows_b + 63) / 64 * 64;
+  HIP_TRY(dcsr.ensure(rows_b));
+  HIP_TRY(dobj.ensure(rec_b));
+  std::vector<int> joined;   // offsets, then the pixel lists: one upload
+  int* rows_src = nullptr;
+  void* rec_dst = recs.data();
+  if (stage) {
+    if (gicp_status st = stage->ensure(rec_off + rec_b)) return st;
+    rows_src = static_cast<int*>(stage->p);
+    rec_dst = static_cast<char*>(stage->p) + rec_off;
+  } else {
+    joined.resize(noff + npix);
+    rows_src = joined.data();
+  }
+  std::memcpy(rows_src, off.data(), sizeof(int) * noff);
+  if (npix) std::memcpy(rows_src + noff, pix.data(), sizeof(int) * npix);
+  HIP_TRY(hipMemcpyAsync(dcsr.p, rows_src, rows_b, hipMemcpyHostToDevice, s));
+  SegObjArgs a{raw, stride, dcsr.as<int>(), dcsr.as<int>() + noff, dobj.as<ddlo_seg_object>()};
+  k_seg_objects<<<L, kObjThreads, 0, s>>>(a);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(rec_dst, dobj.p, rec_b, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (stage) std::memcpy(recs.data(), rec_dst, rec_b);
+  return GICP_OK;
+}
+
 }  // namespace
 }  // namespace ddlo
 
@@ -291,7 +530,16 @@ struct ddlo_seg {
   ddlo_seg_params p{};
   hipStream_t s = nullptr;
   rt::DevBuf raw, range, ground, label;
-  float* pin = nullptr;               // range | label | ground, pinned
+  size_t raw_stride = 0;              // of the scan in raw
+  // objects and the static cloud: the segments' pixel lists and the object
+  // records on the device; the packed scan, the removed pixels and the filter scratch
+  rt::DevBuf zimg, dcsr, dobj, ddrop, f4, f4b, keep, pos, vscratch, cubtmp;
+  bool have_objects = false;
+  std::vector<ddlo_seg_object> objects;   // every segment's record of the last scan (before the ratio test)
+  int* cnt_pin = nullptr;             // pinned: the filters' count read-back
+  ObjStage obj_stage;                 // pinned: the object kernel's pixel lists in, records out
+  ObjStage drop_stage;                // pinned: the removed segments' pixels
+  float* pin = nullptr;               // range | label | z (staged scans) | ground, pinned
   size_t pin_bytes = 0;
   std::vector<float> z;
   // the last scan's images: the pinned read-back buffers themselves (the
@@ -345,8 +593,10 @@ gicp_status ddlo_seg_create(int device, const ddlo_seg_params* p, ddlo_seg** out
   HIP_TRY(hipSetDevice(device));
   HIP_TRY(hipStreamCreateWithFlags(&o->s, hipStreamNonBlocking));
   const size_t n = (size_t)o->p.rows * o->p.cols;
-  o->pin_bytes = n * (sizeof(float) + sizeof(int)) + n;
-  if (hipHostMalloc((void**)&o->pin, o->pin_bytes, hipHostMallocDefault) != hipSuccess) {
+  o->pin_bytes = n * (sizeof(float) + sizeof(int) + sizeof(float)) + n;
+  if (hipHostMalloc((void**)&o->pin, o->pin_bytes, hipHostMallocDefault) != hipSuccess ||
+      hipHostMalloc((void**)&o->cnt_pin, sizeof(int) * 16, hipHostMallocDefault) != hipSuccess) {
+    if (o->pin) (void)hipHostFree(o->pin);
     (void)hipStreamDestroy(o->s);
     return fail(GICP_EHIP, "pinned allocation failed");
   }
@@ -363,25 +613,31 @@ gicp_status ddlo_seg_destroy(ddlo_seg* s) {
   s->ground.reset();
   s->label.reset();
   if (s->pin) (void)hipHostFree(s->pin);
+  if (s->cnt_pin) (void)hipHostFree(s->cnt_pin);
+  s->obj_stage.release();
+  s->drop_stage.release();
   (void)hipStreamDestroy(s->s);
   delete s;
   return GICP_OK;
 }
 
-gicp_status ddlo_seg_process(ddlo_seg* o, const float* xyz_t, size_t stride, const float T[16], const float* residual,
-                             ddlo_seg_result* res) {
-  if (!o || !xyz_t || !T || stride < 12 || stride % 4) return fail(GICP_EINVAL, "invalid argument");
+// ddlo_seg_process; xyz_t == nullptr: the scan is already in o->raw (seg_stage_input)
+static gicp_status seg_run(ddlo_seg* o, const float* xyz_t, size_t stride, const float T[16], const float* residual,
+                           ddlo_seg_result* res) {
   const ddlo_seg_params& p = o->p;
   const int H = p.rows, W = p.cols;
   const size_t n = (size_t)H * W;
   HIP_TRY(hipSetDevice(o->device));
   o->have = false;
+  o->have_objects = false;
   const size_t raw_sz = (n - 1) * stride + 12;
   HIP_TRY(o->raw.ensure(raw_sz));
+  o->raw_stride = stride;
   HIP_TRY(o->range.ensure(sizeof(float) * n));
   HIP_TRY(o->ground.ensure(n));
   HIP_TRY(o->label.ensure(sizeof(int) * n));
-  HIP_TRY(hipMemcpyAsync(o->raw.p, xyz_t, raw_sz, hipMemcpyHostToDevice, o->s));
+  if (xyz_t) HIP_TRY(hipMemcpyAsync(o->raw.p, xyz_t, raw_sz, hipMemcpyHostToDevice, o->s));
+  else HIP_TRY(o->zimg.ensure(sizeof(float) * n));
   SegPixelArgs a{};
   a.raw = o->raw.as<unsigned char>();
   a.stride = stride;
@@ -397,24 +653,33 @@ gicp_status ddlo_seg_process(ddlo_seg* o, const float* xyz_t, size_t stride, con
   a.range = o->range.as<float>();
   a.ground = o->ground.as<signed char>();
   a.label = o->label.as<int>();
+  a.zout = xyz_t ? nullptr : o->zimg.as<float>();
   k_seg_pixels<<<dim3(cdiv_s(W, 256), H), 256, 0, o->s>>>(a);
   HIP_TRY(hipGetLastError());
   float* pin_range = o->pin;
   int* pin_label = reinterpret_cast<int*>(o->pin + n);
-  signed char* pin_ground = reinterpret_cast<signed char*>(pin_label + n);
+  float* pin_z = reinterpret_cast<float*>(pin_label + n);
+  signed char* pin_ground = reinterpret_cast<signed char*>(pin_z + n);
   HIP_TRY(hipMemcpyAsync(pin_range, o->range.p, sizeof(float) * n, hipMemcpyDeviceToHost, o->s));
   HIP_TRY(hipMemcpyAsync(pin_label, o->label.p, sizeof(int) * n, hipMemcpyDeviceToHost, o->s));
   HIP_TRY(hipMemcpyAsync(pin_ground, o->ground.p, n, hipMemcpyDeviceToHost, o->s));
   // the labelling reads cloud_in_t z (:629); gathered while the device works
-  o->z.resize(n);
-  const unsigned char* b = reinterpret_cast<const unsigned char*>(xyz_t);
-  for (size_t i = 0; i < n; ++i) std::memcpy(&o->z[i], b + i * stride + 8, sizeof(float));
+  // (a staged scan's comes back with the images)
+  const float* zsrc = pin_z;
+  if (xyz_t) {
+    o->z.resize(n);
+    const unsigned char* b = reinterpret_cast<const unsigned char*>(xyz_t);
+    for (size_t i = 0; i < n; ++i) std::memcpy(&o->z[i], b + i * stride + 8, sizeof(float));
+    zsrc = o->z.data();
+  } else {
+    HIP_TRY(hipMemcpyAsync(pin_z, o->zimg.p, sizeof(float) * n, hipMemcpyDeviceToHost, o->s));
+  }
   HIP_TRY(hipStreamSynchronize(o->s));
   o->h_range = pin_range;
   o->h_ground = pin_ground;
   o->h_label = pin_label;
   o->hn = n;
-  Labeller lb(p, o->h_range, o->z.data(), residual, o->h_label, T[11], o->avg, o->work);
+  Labeller lb(p, o->h_range, zsrc, residual, o->h_label, T[11], o->avg, o->work);
   lb.run();
   ddlo_seg_result r{};
   r.segments = lb.label_count - 1;
@@ -427,6 +692,12 @@ gicp_status ddlo_seg_process(ddlo_seg* o, const float* xyz_t, size_t stride, con
   o->have = true;
   if (res) *res = r;
   return GICP_OK;
+}
+
+gicp_status ddlo_seg_process(ddlo_seg* o, const float* xyz_t, size_t stride, const float T[16], const float* residual,
+                             ddlo_seg_result* res) {
+  if (!o || !xyz_t || !T || stride < 12 || stride % 4) return fail(GICP_EINVAL, "invalid argument");
+  return seg_run(o, xyz_t, stride, T, residual, res);
 }
 
 gicp_status ddlo_seg_images(ddlo_seg* o, float* range, int8_t* ground, int32_t* label) {
@@ -501,6 +772,174 @@ gicp_status ddlo_seg_label(const ddlo_seg_params* p, const float* range, const f
   lb.run();
   for (size_t l = 0; l < avg_cap; ++l) avg_residual[l] = l < avg.size() ? avg[l] : 0.0;
   if (segments) *segments = lb.label_count - 1;
+  return GICP_OK;
+}
+
+}  // extern "C"
+
+namespace ddlo {
+
+int seg_device(const ddlo_seg* s) { return s->device; }
+
+gicp_status seg_get_params(const ddlo_seg* s, ddlo_seg_params* out) {
+  if (!s || !out) return fail(GICP_EINVAL, "null argument");
+  *out = s->p;
+  return GICP_OK;
+}
+
+gicp_status seg_stage_input(ddlo_seg* o, float4** buf, int* npix) {
+  if (!o || !buf || !npix) return fail(GICP_EINVAL, "null argument");
+  const size_t n = (size_t)o->p.rows * o->p.cols;
+  HIP_TRY(hipSetDevice(o->device));
+  o->have = false;   // the scan in raw is no longer the one the images belong to
+  HIP_TRY(o->raw.ensure(sizeof(float4) * n));
+  *buf = o->raw.as<float4>();
+  *npix = (int)n;
+  return GICP_OK;
+}
+
+gicp_status seg_process_staged(ddlo_seg* o, const float T[16], const float* residual, ddlo_seg_result* res) {
+  if (!o || !T) return fail(GICP_EINVAL, "null argument");
+  return seg_run(o, nullptr, sizeof(float4), T, residual, res);
+}
+
+gicp_status seg_objects_vec(ddlo_seg* o, float max_dim_ratio, std::vector<ddlo_seg_object>& out) {
+  if (!o) return fail(GICP_EINVAL, "null handle");
+  if (!o->have) return fail(GICP_EINVAL, "no processed scan");
+  HIP_TRY(hipSetDevice(o->device));
+  if (!o->have_objects) {
+    gicp_status st = run_objects(o->s, o->raw.as<unsigned char>(), o->raw_stride, o->work.seg_off, o->work.seg_pix,
+                                 o->last.segments, o->dcsr, o->dobj, o->objects, &o->obj_stage);
+    if (st) return st;
+    o->have_objects = true;
+  }
+  filter_objects(o->objects, o->avg.data(), o->avg.size(), max_dim_ratio, out);
+  return GICP_OK;
+}
+
+gicp_status seg_static_cloud_dev(ddlo_seg* o, const int32_t* remove_ids, size_t n_remove, const float centre[3],
+                                 double crop_size, double leaf, const float4** pts, int* count) {
+  if (!o || !pts || !count || !centre || (!remove_ids && n_remove)) return fail(GICP_EINVAL, "invalid argument");
+  if (!o->have) return fail(GICP_EINVAL, "no processed scan");
+  const int L = o->last.segments;
+  const std::vector<int>& off = o->work.seg_off;
+  size_t ndrop = 0;
+  for (size_t k = 0; k < n_remove; ++k) {
+    if (remove_ids[k] < 1 || remove_ids[k] > L) return fail(GICP_EINVAL, "remove_ids names no segment of the last scan");
+    ndrop += (size_t)(off[remove_ids[k] + 1] - off[remove_ids[k]]);
+  }
+  HIP_TRY(hipSetDevice(o->device));
+  const int n = (int)o->hn;
+  // the removed segments' pixels (an id named twice is listed twice: harmless)
+  if (gicp_status st = o->drop_stage.ensure(sizeof(int) * std::max<size_t>(ndrop, 1))) return st;
+  int* const drop = static_cast<int*>(o->drop_stage.p);
+  size_t w = 0;
+  for (size_t k = 0; k < n_remove; ++k) {
+    const int b = off[remove_ids[k]], e = off[remove_ids[k] + 1];
+    std::memcpy(drop + w, o->work.seg_pix.data() + b, sizeof(int) * (size_t)(e - b));
+    w += (size_t)(e - b);
+  }
+  HIP_TRY(o->ddrop.ensure(sizeof(int) * std::max<size_t>(ndrop, 1)));
+  HIP_TRY(o->f4.ensure(sizeof(float4) * (size_t)n));
+  HIP_TRY(o->f4b.ensure(sizeof(float4) * (size_t)n));
+  HIP_TRY(o->keep.ensure(sizeof(int) * (size_t)n));
+  HIP_TRY(o->pos.ensure(sizeof(int) * (size_t)n));
+  HIP_TRY(o->vscratch.ensure(sizeof(int) * voxel_scratch_ints(n)));
+  HIP_TRY(o->cubtmp.ensure(std::max(crop_box_tmp_bytes(n), voxel_tmp_bytes(n))));
+  launch_pack4(o->s, o->raw.as<unsigned char>(), o->raw_stride, n, o->f4.as<float4>());
+  if (ndrop) {
+    HIP_TRY(hipMemcpyAsync(o->ddrop.p, drop, sizeof(int) * ndrop, hipMemcpyHostToDevice, o->s));
+    k_static_drop<<<cdiv_s((long)ndrop, 256), 256, 0, o->s>>>(o->ddrop.as<int>(), (int)ndrop, o->f4.as<float4>());
+  }
+  HIP_TRY(hipGetLastError());
+  const CropCentre cc{centre[0], centre[1], centre[2]};
+  const bool crop = crop_size > 0;
+  int m = -1;
+  if (leaf > 0) {   // the crop box folded into the voxel pass (as the driver's preprocessing does)
+    if (voxel_grid(o->s, o->f4.as<float4>(), n, (float)leaf, o->f4b.as<float4>(), o->vscratch.as<int>(), o->cubtmp.p,
+                   o->cubtmp.bytes, &m, crop ? (float)crop_size : 0.f, o->cnt_pin, cc))
+      return fail(GICP_EHIP, "voxel filter scratch too small");
+  }
+  if (m < 0) {   // no voxel filter, or its grid overflows (the reference then keeps the cloud as it is)
+    if (crop_box(o->s, o->f4.as<float4>(), n, (float)crop_size, o->f4b.as<float4>(), o->keep.as<int>(), o->pos.as<int>(),
+                 o->cubtmp.p, o->cubtmp.bytes, &m, o->cnt_pin, cc, crop))
+      return fail(GICP_EHIP, "crop box scratch too small");
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(o->s));
+  *pts = o->f4b.as<float4>();
+  *count = m;
+  return GICP_OK;
+}
+
+}  // namespace ddlo
+
+extern "C" {
+
+gicp_status ddlo_seg_objects(ddlo_seg* o, float max_dim_ratio, ddlo_seg_object* out, size_t cap, size_t* n) {
+  if (!o || !n || (!out && cap)) return fail(GICP_EINVAL, "invalid argument");
+  std::vector<ddlo_seg_object> v;
+  gicp_status st = seg_objects_vec(o, max_dim_ratio, v);
+  if (st) return st;
+  for (size_t i = 0; i < v.size() && i < cap; ++i) out[i] = v[i];
+  *n = v.size();
+  return GICP_OK;
+}
+
+gicp_status ddlo_seg_objects_from(int device, const float* xyz_t, size_t stride, int rows, int cols, const int32_t* label,
+                                  const double* avg_residual, size_t avg_n, float max_dim_ratio, ddlo_seg_object* out,
+                                  size_t cap, size_t* n) {
+  if (!xyz_t || !label || !n || (!out && cap) || stride < 12 || stride % 4 || rows < 1 || cols < 1 ||
+      (long)rows * cols > INT32_MAX / 4)
+    return fail(GICP_EINVAL, "invalid argument");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+    return fail(GICP_EHIP, "no HIP device " + std::to_string(device) + " (HIP library present, device not visible)");
+  HIP_TRY(hipSetDevice(device));
+  const size_t np = (size_t)rows * cols;
+  // every label's pixels, row-major, as CSR (a counting sort, as ddlo_seg_label_indices)
+  int L = 0;
+  for (size_t i = 0; i < np; ++i)
+    if (label[i] > L && label[i] != kRejected) L = label[i];
+  std::vector<int> off((size_t)L + 2, 0);
+  for (size_t i = 0; i < np; ++i)
+    if (label[i] > 0 && label[i] != kRejected) ++off[label[i] + 1];
+  for (int l = 1; l <= L + 1; ++l) off[l] += off[l - 1];
+  std::vector<int> pix((size_t)off[L + 1]), at(off.begin(), off.end() - 1);
+  for (size_t i = 0; i < np; ++i)
+    if (label[i] > 0 && label[i] != kRejected) pix[at[label[i]]++] = (int)i;
+  DevBuf raw, dcsr, dobj;
+  const size_t raw_sz = (np - 1) * stride + 12;
+  HIP_TRY(raw.ensure(raw_sz));
+  hipStream_t s = nullptr;   // the null stream: the copy below is synchronous with it
+  HIP_TRY(hipMemcpy(raw.p, xyz_t, raw_sz, hipMemcpyHostToDevice));
+  std::vector<ddlo_seg_object> recs, v;
+  gicp_status st = run_objects(s, raw.as<unsigned char>(), stride, off, pix, L, dcsr, dobj, recs, nullptr);
+  if (st) return st;
+  filter_objects(recs, avg_residual, avg_residual ? avg_n : 0, max_dim_ratio, v);
+  for (size_t i = 0; i < v.size() && i < cap; ++i) out[i] = v[i];
+  *n = v.size();
+  return GICP_OK;
+}
+
+gicp_status ddlo_seg_static_cloud(ddlo_seg* o, const int32_t* remove_ids, size_t n_remove, const float centre[3],
+                                  double crop_size, double leaf, float* out, size_t cap, size_t* nout) {
+  if (!nout || (!out && cap)) return fail(GICP_EINVAL, "invalid argument");
+  const float4* pts = nullptr;
+  int m = 0;
+  gicp_status st = seg_static_cloud_dev(o, remove_ids, n_remove, centre, crop_size, leaf, &pts, &m);
+  if (st) return st;
+  *nout = (size_t)m;
+  if (!out || m == 0) return GICP_OK;
+  if ((size_t)m > cap) return fail(GICP_EINVAL, "output capacity too small");
+  std::vector<float4> h((size_t)m);
+  HIP_TRY(hipMemcpyAsync(h.data(), pts, sizeof(float4) * (size_t)m, hipMemcpyDeviceToHost, o->s));
+  HIP_TRY(hipStreamSynchronize(o->s));
+  for (int i = 0; i < m; ++i) {
+    out[3 * i] = h[i].x;
+    out[3 * i + 1] = h[i].y;
+    out[3 * i + 2] = h[i].z;
+  }
   return GICP_OK;
 }
 

@@ -13,9 +13,10 @@ import ctypes as C
 import numpy as np
 
 from . import GicpError, GicpParams, GicpResult, _ptr, load
+from .segmentation import OBJECT_DTYPE, SegObject, SegResult, Segmentation
 
-__all__ = ["OdomParams", "OdomResult", "Odometry", "default_odom_params", "preprocess", "convex_hull",
-           "concave_hull", "TRACKED", "FIRST", "SKIPPED", "INIT"]
+__all__ = ["OdomParams", "OdomResult", "DynamicParams", "NONSTATIC_FN", "Odometry", "default_odom_params",
+           "default_dynamic_params", "preprocess", "convex_hull", "concave_hull", "TRACKED", "FIRST", "SKIPPED", "INIT"]
 
 TRACKED, FIRST, SKIPPED, INIT = 0, 1, 2, 3
 
@@ -64,6 +65,15 @@ class OdomResult(C.Structure):
         return np.array(self.T, dtype=np.float32).reshape(4, 4)
 
 
+class DynamicParams(C.Structure):
+    """ddlo_dynamic_params."""
+    _fields_ = [("theta_min", C.c_double), ("theta_max", C.c_double), ("max_dim_ratio", C.c_float)]
+
+
+# ddlo_nonstatic_fn: int (*)(void* user, const ddlo_seg_object* objs, size_t n, uint8_t* non_static)
+NONSTATIC_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(SegObject), C.c_size_t, C.POINTER(C.c_uint8))
+
+
 _SIGS_DONE = False
 
 
@@ -78,6 +88,10 @@ def _lib():
             "ddlo_odom_destroy": (I, [P]),
             "ddlo_odom_process": (I, [P, P, S, S, C.POINTER(OdomResult)]),
             "ddlo_odom_keyframe": (I, [P, I, P, C.POINTER(S)]),
+            "ddlo_odom_keyframe_points": (I, [P, I, P, S, C.POINTER(S)]),
+            "ddlo_dynamic_default_params": (I, [C.POINTER(DynamicParams)]),
+            "ddlo_odom_process_dynamic": (I, [P, P, P, S, C.POINTER(DynamicParams), NONSTATIC_FN, P,
+                                              C.POINTER(OdomResult), C.POINTER(SegResult)]),
             "ddlo_odom_submap": (I, [P, P, S, C.POINTER(S)]),
             "ddlo_odom_ctx": (I, [P, I, C.POINTER(P)]),
             "ddlo_preprocess": (I, [I, P, S, S, D, D, P, S, C.POINTER(S)]),
@@ -101,6 +115,15 @@ def default_odom_params(**kw) -> OdomParams:
     """cfg/ddlo.yaml defaults (odom.cc:196-252)."""
     p = OdomParams()
     _check(_lib().ddlo_odom_default_params(C.byref(p)))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_dynamic_params(**kw) -> DynamicParams:
+    """The residual image's window (odom.cc:804-805) and detection/maxDimRatio."""
+    p = DynamicParams()
+    _check(_lib().ddlo_dynamic_default_params(C.byref(p)))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -134,6 +157,53 @@ class Odometry:
         r = OdomResult()
         _check(self.L.ddlo_odom_process(self.h, _ptr(a), a.shape[0], 12, C.byref(r)))
         return r
+
+    def process_dynamic(self, seg: Segmentation, scan, decide=None, params: DynamicParams | None = None):
+        """ddlo_odom_process_dynamic: one organized sensor-frame scan (seg's rows*cols points, NaN = no
+        return).  decide(objects) -> iterable of truth values, one per object (true: cut it out), or
+        None to abort; objects is an OBJECT_DTYPE array.  decide=None: every object is non-static.
+        Returns (OdomResult, SegResult)."""
+        a = np.ascontiguousarray(scan, np.float32)
+        if a.ndim != 2 or a.shape[0] != seg.params.rows * seg.params.cols or a.shape[1] < 3:
+            raise ValueError("scan must be (rows*cols, >=3)")
+        raised = []
+
+        def trampoline(_user, objs, n, flags):
+            try:
+                arr = np.zeros(n, OBJECT_DTYPE)
+                if n:
+                    C.memmove(arr.ctypes.data, objs, n * C.sizeof(SegObject))
+                verdict = decide(arr)
+                if verdict is None:
+                    return 1
+                verdict = list(verdict)
+                if len(verdict) != n:
+                    raise ValueError("decide must return one verdict per object")
+                for i, v in enumerate(verdict):
+                    flags[i] = 1 if v else 0
+                return 0
+            except BaseException as e:   # never unwind through the C frames
+                raised.append(e)
+                return 1
+
+        cb = NONSTATIC_FN(trampoline) if decide is not None else C.cast(None, NONSTATIC_FN)
+        r, sr = OdomResult(), SegResult()
+        st = self.L.ddlo_odom_process_dynamic(self.h, seg.h, _ptr(a), a.shape[1] * 4,
+                                              C.byref(params) if params is not None else None, cb, None,
+                                              C.byref(r), C.byref(sr))
+        if raised:
+            raise raised[0]
+        _check(st)
+        seg.last = sr
+        return r, sr
+
+    def keyframe_points(self, k: int) -> np.ndarray:
+        """World-frame points of keyframe k (after the submap voxel filter), (n, 3) float32."""
+        n = C.c_size_t()
+        _check(self.L.ddlo_odom_keyframe_points(self.h, k, None, 0, C.byref(n)))
+        out = np.zeros((max(n.value, 1), 3), np.float32)
+        _check(self.L.ddlo_odom_keyframe_points(self.h, k, _ptr(out), out.shape[0], C.byref(n)))
+        return out[:n.value]
 
     def keyframe(self, k: int):
         pose = (C.c_float * 7)()

@@ -14,8 +14,8 @@ import numpy as np
 
 from . import GicpError, _ptr, load
 
-__all__ = ["SegParams", "SegResult", "Segmentation", "default_seg_params", "yaml_seg_params", "label_components",
-           "EXCLUDED", "UNLABELLED", "REJECTED"]
+__all__ = ["SegParams", "SegResult", "SegObject", "OBJECT_DTYPE", "Segmentation", "default_seg_params",
+           "yaml_seg_params", "label_components", "objects_from", "EXCLUDED", "UNLABELLED", "REJECTED"]
 
 EXCLUDED, UNLABELLED, REJECTED = -1, 0, 999999
 
@@ -60,6 +60,23 @@ class SegResult(C.Structure):
     ]
 
 
+class SegObject(C.Structure):
+    """ddlo_seg_object: one detected object (getObject / computeAllObjects)."""
+    _fields_ = [
+        ("id", C.c_int32),
+        ("num_points", C.c_int32),
+        ("state", C.c_float * 7),
+        ("axis", C.c_float * 2),
+        ("density", C.c_float),
+        ("avg_residuum", C.c_double),
+    ]
+
+
+# the same layout as a numpy structured type (objects() returns such an array)
+OBJECT_DTYPE = np.dtype([("id", np.int32), ("num_points", np.int32), ("state", np.float32, 7),
+                         ("axis", np.float32, 2), ("density", np.float32), ("avg_residuum", np.float64)], align=True)
+
+
 _SIGS_DONE = False
 
 
@@ -78,6 +95,9 @@ def _lib():
             "ddlo_seg_ground_indices": (I, [P, P, S, C.POINTER(S)]),
             "ddlo_seg_label_indices": (I, [P, P, S, P, S, C.POINTER(S)]),
             "ddlo_seg_label": (I, [C.POINTER(SegParams), P, P, P, F, P, P, S, C.POINTER(C.c_int32)]),
+            "ddlo_seg_objects": (I, [P, F, P, S, C.POINTER(S)]),
+            "ddlo_seg_objects_from": (I, [I, P, S, I, I, P, P, S, F, P, S, C.POINTER(S)]),
+            "ddlo_seg_static_cloud": (I, [P, P, S, P, C.c_double, C.c_double, P, S, C.POINTER(S)]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -126,6 +146,28 @@ def label_components(p: SegParams, range_img, z_img, label_img, sensor_z: float,
     _check(_lib().ddlo_seg_label(C.byref(p), _ptr(rng), _ptr(z), None if res is None else _ptr(res), float(sensor_z),
                                  _ptr(lab), _ptr(avg), avg.size, C.byref(seg)))
     return lab.reshape(p.rows, p.cols), avg[: seg.value + 1], seg.value
+
+
+def objects_from(xyz_t, label, avg_residual=None, max_dim_ratio: float = 10.0, device: int = 0) -> np.ndarray:
+    """ddlo_seg_objects_from: the objects of a caller's label image (rows x cols) over the organized
+    world-frame cloud xyz_t (rows*cols, >=3); returns an OBJECT_DTYPE array."""
+    lab = np.ascontiguousarray(label, np.int32)
+    if lab.ndim != 2:
+        raise ValueError("label must be a rows x cols image")
+    rows, cols = lab.shape
+    a = np.ascontiguousarray(xyz_t, np.float32)
+    if a.ndim != 2 or a.shape[0] != rows * cols or a.shape[1] < 3:
+        raise ValueError("xyz_t must be (rows*cols, >=3)")
+    avg = None if avg_residual is None else np.ascontiguousarray(avg_residual, np.float64).reshape(-1)
+    L = _lib()
+    n = C.c_size_t()
+    args = (device, _ptr(a), a.shape[1] * 4, rows, cols, _ptr(lab), None if avg is None else _ptr(avg),
+            0 if avg is None else avg.size, float(max_dim_ratio))
+    _check(L.ddlo_seg_objects_from(*args, None, 0, C.byref(n)))
+    out = np.zeros(n.value, OBJECT_DTYPE)
+    if n.value:
+        _check(L.ddlo_seg_objects_from(*args, _ptr(out), out.size, C.byref(n)))
+    return out
 
 
 class Segmentation:
@@ -198,3 +240,24 @@ class Segmentation:
         _check(self.L.ddlo_seg_label_indices(self.h, _ptr(off), off.size, _ptr(idx), idx.size, C.byref(n)))
         return [None] + [idx[off[l]:off[l + 1]] for l in range(1, L + 1)]
 
+
+    def objects(self, max_dim_ratio: float = 10.0) -> np.ndarray:
+        """computeAllObjects: the objects of the last process(), ascending id, as an OBJECT_DTYPE array."""
+        n = C.c_size_t()
+        _check(self.L.ddlo_seg_objects(self.h, float(max_dim_ratio), None, 0, C.byref(n)))
+        out = np.zeros(n.value, OBJECT_DTYPE)
+        if n.value:
+            _check(self.L.ddlo_seg_objects(self.h, float(max_dim_ratio), _ptr(out), out.size, C.byref(n)))
+        return out
+
+    def static_cloud(self, remove_ids=(), centre=(0.0, 0.0, 0.0), crop_size: float = 0.0, leaf: float = 0.0):
+        """applySegmentation's tail (odom.cc:887-918): the last scan without the pixels of the segments in
+        remove_ids, cropped around centre and voxel-filtered; (m, 3) float32."""
+        ids = np.ascontiguousarray(remove_ids, np.int32).reshape(-1)
+        c = np.ascontiguousarray(centre, np.float32).reshape(3)
+        n = C.c_size_t()
+        args = (self.h, _ptr(ids) if ids.size else None, ids.size, _ptr(c), float(crop_size), float(leaf))
+        _check(self.L.ddlo_seg_static_cloud(*args, None, 0, C.byref(n)))
+        out = np.zeros((max(n.value, 1), 3), np.float32)
+        _check(self.L.ddlo_seg_static_cloud(*args, _ptr(out), out.shape[0], C.byref(n)))
+        return out[:n.value]

@@ -12,14 +12,23 @@
  * scans, keyframe clouds, their covariances and the submap — stays in device
  * memory; the host keeps only poses and index lists.
  *
+ * ddlo_odom_process_dynamic adds the step that makes the reference *Dynamic*
+ * DLO (odom.cc:685-693, :853-918): every tracked scan is segmented
+ * (ddlo_segment.h), its segments become objects, and the objects the caller's
+ * tracker does not know to be static are cut out of the scan before it may
+ * become a keyframe, so that moving things never enter the submap.
+ *
  * Not restated (outside the GICP path): ROS I/O, IMU gravity
- * alignment, the organized-cloud row/col downsampling filter, dynamic-object
- * detection and tracking, publishing and trajectory files.
+ * alignment, the organized-cloud row/col downsampling filter (odom.cc:902-906),
+ * the object tracker itself (trackDetections and the bounding-box Kalman
+ * filter: its verdict enters through ddlo_nonstatic_fn), publishing and
+ * trajectory files.
  */
 #ifndef DDLO_ODOM_H
 #define DDLO_ODOM_H
 
 #include "ddlo_gicp.h"
+#include "ddlo_segment.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -88,6 +97,38 @@ gicp_status ddlo_odom_process(struct ddlo_odom* o, const float* xyz, size_t n, s
 /* Keyframe k: world pose (x, y, z, qx, qy, qz, qw as the reference's pose_ /
  * rotq_) and its point count (after the submap voxel filter). */
 gicp_status ddlo_odom_keyframe(const struct ddlo_odom* o, int k, float pose7[7], size_t* npoints);
+/* Points of keyframe k (world frame, after the submap voxel filter): x, y, z
+ * float, 12 B each; xyz[i] for i < cap, *n = the keyframe's point count. */
+gicp_status ddlo_odom_keyframe_points(const struct ddlo_odom* o, int k, float* xyz, size_t cap, size_t* n);
+
+/* The dynamic-object step of OdomNode::icpCB (odom.cc:685-693). */
+typedef struct ddlo_dynamic_params {
+  double theta_min, theta_max;     /* the residual image's angular window (odom.cc:804-805: -60 deg, +60 deg), rad */
+  float max_dim_ratio;             /* odomNode/detection/maxDimRatio (10.0) */
+} ddlo_dynamic_params;
+gicp_status ddlo_dynamic_default_params(ddlo_dynamic_params* out);
+/* The tracker's verdict: set non_static[i] = 1 for the objects to cut out
+ * (ObjectStatus UNDEFINED or DYNAMIC); non_static arrives zeroed.  Return
+ * non-zero to abort (ddlo_odom_process_dynamic then returns GICP_ESTATE and
+ * the driver is unusable).  A NULL callback treats every detected object as
+ * non-static, which is what the reference does with an object during its
+ * first frames (bounding_box_filter.cpp:178-186). */
+typedef int (*ddlo_nonstatic_fn)(void* user, const ddlo_seg_object* objs, size_t n, uint8_t* non_static);
+/* ddlo_odom_process for one organized sensor-frame scan of seg's rows x cols
+ * pixels (NaN = no return): the registration half is ddlo_odom_process on
+ * that buffer, bit for bit.  On a TRACKED frame, between pose propagation and
+ * updateKeyframes: the world-frame scan T_ * xyz (device) -> the S2M
+ * context's residual image at seg's size -> ddlo_seg_process -> ddlo_seg_objects
+ * -> decide.  If updateKeyframes then adds a keyframe, its cloud is
+ * ddlo_seg_static_cloud without the non-static objects (crop centre pose_,
+ * crop_size when crop_use, vf_scan_res when vf_scan_use), followed by the
+ * submap voxel filter and the S2S-k covariances as for every keyframe.  The
+ * first keyframe (initializeInputTarget) is the registration scan, as in
+ * ddlo_odom_process.  INIT, FIRST and SKIPPED frames run no segmentation and
+ * zero *seg_res.  dp NULL: the defaults; seg_res may be NULL. */
+gicp_status ddlo_odom_process_dynamic(struct ddlo_odom* o, struct ddlo_seg* seg, const float* xyz, size_t stride_bytes,
+                                      const ddlo_dynamic_params* dp, ddlo_nonstatic_fn decide, void* user,
+                                      ddlo_odom_result* res, ddlo_seg_result* seg_res);
 /* Keyframe indices of the current submap (sorted, submap_kf_idx_prev_). */
 gicp_status ddlo_odom_submap(const struct ddlo_odom* o, int32_t* idx, size_t cap, size_t* n);
 /* The S2S (which = 0) or S2M (which = 1) GICP context, for the gicp_* getters

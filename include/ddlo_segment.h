@@ -18,10 +18,28 @@
  *   ddlo_seg_ground_indices   getGroundIndices :1002-1013
  *   ddlo_seg_label_indices    label_indices_i_ (cloudSegmentation :524-538)
  *   ddlo_seg_label     labelComponents over caller-provided images (host only)
+ *   ddlo_seg_objects / ddlo_seg_objects_from
+ *                      computeAllObjects / getObject :726-818: one oriented
+ *                      bounding box per segment, on the device (one workgroup
+ *                      per segment)
+ *   ddlo_seg_static_cloud   the part of OdomNode::applySegmentation after the
+ *                      detection (odom.cc:867-918): the scan without the
+ *                      pixels of the non-static objects, cropped around the
+ *                      pose and voxel-filtered, on the device
  *
- * Bounding boxes, tracking, visualisation and evaluation (computeAllObjects,
- * trackDetections, visualize, evaluate) are outside the registration path and
- * not restated.
+ * The tracker that decides which objects are static (trackDetections, the
+ * bounding-box Kalman filter), visualisation and evaluation are not restated:
+ * the caller decides (ddlo_odom_process_dynamic takes that verdict as a
+ * callback, ddlo_odom.h).
+ *
+ * Eigenvector convention of the boxes.  getObject takes the principal axes of
+ * a segment's (x, y) covariance from Eigen's SelfAdjointEigenSolver, whose
+ * eigenvector signs are not part of Eigen's contract.  Here `axis` is the unit
+ * eigenvector of the SMALLER eigenvalue (Eigen sorts ascending, so this is
+ * eigen_vectors_PCA.col(0)) with axis[0] > 0, or axis[0] == 0 and axis[1] > 0;
+ * the second axis is (-axis[1], axis[0]); equal eigenvalues (a single point
+ * included) give axis = (1, 0).  A box's centre and dimensions do not depend
+ * on the signs chosen; only state[3] = sin(orientation / 2) does.
  */
 #ifndef DDLO_SEGMENT_H
 #define DDLO_SEGMENT_H
@@ -116,5 +134,8 @@ gicp_status ddlo_seg_label(const ddlo_seg_params* p, const float* range, const f
 #ifdef __cplusplus
 }
 #endif
+
+/* ddlo_seg_object, ddlo_seg_objects, ddlo_seg_objects_from, ddlo_seg_static_cloud */
+#include "ddlo_seg_objects.h"
 
 #endif /* DDLO_SEGMENT_H */
