@@ -120,6 +120,10 @@ struct CropCentre {
 int crop_box(hipStream_t s, const float4* in, int n, float size, float4* out, int* keep, int* pos, void* tmp,
              size_t tmp_bytes, int* count_host, int* pin, CropCentre centre = CropCentre(), bool box = true);
 size_t crop_box_tmp_bytes(int n);
+// crop_box's second half on flags of the caller's (keep[i] = 0 / 1): the
+// flagged points to out in input order; scratch and pin as for crop_box
+int compact_flagged(hipStream_t s, const float4* in, int n, float4* out, const int* keep, int* pos, void* tmp,
+                    size_t tmp_bytes, int* count_host, int* pin);
 // crop > 0: the crop box (points inside [-crop, crop]^3 removed) folded into the same pass
 int voxel_grid(hipStream_t s, const float4* in, int n, float leaf, float4* out, int* scratch, void* tmp, size_t tmp_bytes,
                int* count_host, float crop, int* pin, CropCentre centre = CropCentre());

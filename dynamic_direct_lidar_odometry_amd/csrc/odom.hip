@@ -51,6 +51,7 @@
 #include "runtime.hpp"
 #include "devknobs.hpp"
 #include "seg_internal.hpp"
+#include "odom_internal.hpp"
 
 namespace {
 
@@ -1184,3 +1185,16 @@ gicp_status ddlo_concave_hull(const float* xyz, int n, double alpha, int32_t* id
 }
 
 }  // extern "C"
+
+// odom_internal.hpp: keyframe k's cloud where it lives (the global map reads it device to device)
+gicp_status ddlo::odom_keyframe_dev(const ddlo_odom* o, int k, const float4** pts, int* n, int* device,
+                                    hipStream_t* stream) {
+  if (!o || !pts || !n || !device || !stream || k < 0 || k >= (int)o->keyframes.size())
+    return fail(GICP_EINVAL, "invalid keyframe index");
+  const Keyframe& kf = *o->keyframes[k];
+  *pts = kf.pts.as<float4>();
+  *n = kf.n;
+  *device = o->device;
+  *stream = o->s;
+  return GICP_OK;
+}

@@ -256,6 +256,14 @@ int crop_box(hipStream_t s, const float4* in, int n, float size, float4* out, in
     return 0;
   }
   k_crop_flags<<<cdiv_l(n, 256), 256, 0, s>>>(in, n, size, centre, box ? 1 : 0, keep);
+  return compact_flagged(s, in, n, out, keep, pos, tmp, tmp_bytes, count_host, pin);
+}
+int compact_flagged(hipStream_t s, const float4* in, int n, float4* out, const int* keep, int* pos, void* tmp,
+                    size_t tmp_bytes, int* count_host, int* pin) {
+  if (n <= 0) {
+    *count_host = 0;
+    return 0;
+  }
   size_t need = 0;
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, need, keep, pos, n, s);
   if (need > tmp_bytes) return -1;
