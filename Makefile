@@ -8,51 +8,21 @@ PKG := dynamic_direct_lidar_odometry_amd
 CSRC := $(PKG)/csrc
 LIBDIR := $(PKG)/_lib
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function
-OBJS := $(LIBDIR)/kernels.o $(LIBDIR)/knn_tasks.o $(LIBDIR)/nftree.o $(LIBDIR)/cellgrid.o $(LIBDIR)/tietree.o $(LIBDIR)/capi.o $(LIBDIR)/preprocess.o $(LIBDIR)/odom.o $(LIBDIR)/segment.o $(LIBDIR)/map.o
+# the hot path, one file per stage (K1 .. K6), then the other translation units
+STAGES := index_build covariance corr_search moments outputs
+SRCS := $(STAGES) knn_tasks nftree cellgrid tietree capi preprocess odom segment map
+OBJS := $(SRCS:%=$(LIBDIR)/%.o)
 
 all: lib oracle facade raycast
 
 lib: $(LIBDIR)/libddlo_gicp.so
 
-$(LIBDIR)/kernels.o: $(CSRC)/kernels.hip $(CSRC)/search.hpp $(CSRC)/nn_tasks.hpp $(CSRC)/cov_math.hpp $(CSRC)/gicp_types.hpp $(CSRC)/launch.hpp
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+# every object from its .hip; the compiler writes the header dependencies (.d)
+$(LIBDIR)/%.o: $(CSRC)/%.hip
+	@mkdir -p $(@D)
+	$(HIPCC) $(HIPFLAGS) -MMD -MP -c $< -o $@
 
-$(LIBDIR)/knn_tasks.o: $(CSRC)/knn_tasks.hip $(CSRC)/search.hpp $(CSRC)/nn_tasks.hpp $(CSRC)/cov_math.hpp $(CSRC)/gicp_types.hpp $(CSRC)/launch.hpp
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/nftree.o: $(CSRC)/nftree.hip $(CSRC)/nftree.hpp $(CSRC)/cov_math.hpp $(CSRC)/gicp_types.hpp $(CSRC)/launch.hpp
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/cellgrid.o: $(CSRC)/cellgrid.hip $(CSRC)/cellgrid.hpp $(CSRC)/search.hpp $(CSRC)/gicp_types.hpp
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/tietree.o: $(CSRC)/tietree.hip $(CSRC)/gicp_types.hpp $(CSRC)/launch.hpp
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/capi.o: $(CSRC)/capi.hip $(CSRC)/nftree.hpp $(CSRC)/runtime.hpp $(CSRC)/cellgrid.hpp $(CSRC)/gicp_types.hpp $(CSRC)/launch.hpp include/ddlo_gicp.h
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/preprocess.o: $(CSRC)/preprocess.hip $(CSRC)/gicp_types.hpp $(CSRC)/launch.hpp
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/odom.o: $(CSRC)/odom.hip $(CSRC)/runtime.hpp $(CSRC)/gicp_types.hpp $(CSRC)/launch.hpp $(CSRC)/seg_internal.hpp $(CSRC)/odom_internal.hpp include/ddlo_gicp.h include/ddlo_odom.h include/ddlo_segment.h include/ddlo_seg_objects.h
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/segment.o: $(CSRC)/segment.hip $(CSRC)/runtime.hpp $(CSRC)/gicp_types.hpp $(CSRC)/launch.hpp $(CSRC)/seg_internal.hpp include/ddlo_gicp.h include/ddlo_segment.h include/ddlo_seg_objects.h
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(LIBDIR)/map.o: $(CSRC)/map.hip $(CSRC)/runtime.hpp $(CSRC)/gicp_types.hpp $(CSRC)/launch.hpp $(CSRC)/odom_internal.hpp include/ddlo_gicp.h include/ddlo_odom.h include/ddlo_segment.h include/ddlo_seg_objects.h include/ddlo_map.h
-	@mkdir -p $(LIBDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+-include $(OBJS:.o=.d)
 
 $(LIBDIR)/libddlo_gicp.so: $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined -o $@ $(OBJS)
@@ -72,40 +42,37 @@ tests/cpp/facade_replay: tests/cpp/facade_replay.cpp include/nano_gicp/nano_gicp
 	g++ -std=c++17 -O2 -Iinclude -o $@ tests/cpp/facade_replay.cpp -L$(LIBDIR) -lddlo_gicp -Wl,-rpath,'$$ORIGIN/../../$(LIBDIR)'
 
 clean:
-	rm -f $(LIBDIR)/*.o $(LIBDIR)/*.so tests/cpp/facade_replay tools/raycast/libddlo_raycast.so
+	rm -f $(LIBDIR)/*.o $(LIBDIR)/*.d $(LIBDIR)/*/*.o $(LIBDIR)/*/*.d $(LIBDIR)/*.so tests/cpp/facade_replay tools/raycast/libddlo_raycast.so
 	$(MAKE) -C oracle clean
 
 .PHONY: all lib oracle facade raycast clean
 
-# developer variant: k_lm_step prints per-phase cycle counts (load with DDLO_GICP_LIB)
-lmprof: $(OBJS)
-	@mkdir -p $(LIBDIR)/lmprof
-	$(HIPCC) $(HIPFLAGS) -DDDLO_LM_PROF -c $(CSRC)/kernels.hip -o $(LIBDIR)/lmprof/kernels.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(LIBDIR)/lmprof/libddlo_gicp.so $(LIBDIR)/lmprof/kernels.o $(filter-out $(LIBDIR)/kernels.o,$(OBJS))
+# Developer variants (load with DDLO_GICP_LIB): one stage file recompiled with a
+# profile define, linked with the product's other objects.
+#   lmprof    the LM step prints per-phase cycle counts
+#   statsprof the search kernels fill the per-sub-group counters of gicp_debug_stats (tools/probe_tasks.py)
+#   covprof   k_covariances2 stores per-group stamps (tools/cov_timeline.py)
+# $(call VARIANT,name,defines,stage)
+define VARIANT
+$(LIBDIR)/$(1)/$(3).o: $(CSRC)/$(3).hip
+	@mkdir -p $$(@D)
+	$(HIPCC) $(HIPFLAGS) $(2) -MMD -MP -c $$< -o $$@
+$(LIBDIR)/$(1)/libddlo_gicp.so: $(LIBDIR)/$(1)/$(3).o $(filter-out $(LIBDIR)/$(3).o,$(OBJS))
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $$@ $$^
+$(1): $(LIBDIR)/$(1)/libddlo_gicp.so
+.PHONY: $(1)
+-include $(LIBDIR)/$(1)/$(3).d
+endef
+$(eval $(call VARIANT,lmprof,-DDDLO_LM_PROF,moments))
+$(eval $(call VARIANT,statsprof,-DDDLO_SEARCH_STATS,corr_search))
+$(eval $(call VARIANT,covprof,-DDDLO_COV_PROF -DDDLO_DEV,covariance))
 
-.PHONY: lmprof
-
-# developer variant: the search kernels fill the per-sub-group counters of
-# gicp_debug_stats (tools/probe_tasks.py; load with DDLO_GICP_LIB)
-statsprof: $(OBJS)
-	@mkdir -p $(LIBDIR)/statsprof
-	$(HIPCC) $(HIPFLAGS) -DDDLO_SEARCH_STATS -c $(CSRC)/kernels.hip -o $(LIBDIR)/statsprof/kernels.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(LIBDIR)/statsprof/libddlo_gicp.so $(LIBDIR)/statsprof/kernels.o $(filter-out $(LIBDIR)/kernels.o,$(OBJS))
-
-.PHONY: statsprof
-
-# developer variant: k_covariances2 stores per-group stamps (tools/cov_timeline.py; load with DDLO_GICP_LIB)
-covprof: $(OBJS)
-	@mkdir -p $(LIBDIR)/covprof
-	$(HIPCC) $(HIPFLAGS) -DDDLO_COV_PROF -DDDLO_DEV -c $(CSRC)/kernels.hip -o $(LIBDIR)/covprof/kernels.o
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(LIBDIR)/covprof/libddlo_gicp.so $(LIBDIR)/covprof/kernels.o $(filter-out $(LIBDIR)/kernels.o,$(OBJS))
-
-.PHONY: covprof
-
-# development build: the A/B environment knobs (devknobs.hpp) are read
-dev:
-	@mkdir -p $(LIBDIR)/dev
-	for f in $(notdir $(OBJS:.o=)); do $(HIPCC) $(HIPFLAGS) -DDDLO_DEV -c $(CSRC)/$$f.hip -o $(LIBDIR)/dev/$$f.o || exit 1; done
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(LIBDIR)/dev/libddlo_gicp.so $(addprefix $(LIBDIR)/dev/,$(notdir $(OBJS)))
-
+# development build: every file with the A/B environment knobs (devknobs.hpp) read
+$(LIBDIR)/dev/%.o: $(CSRC)/%.hip
+	@mkdir -p $(@D)
+	$(HIPCC) $(HIPFLAGS) -DDDLO_DEV -MMD -MP -c $< -o $@
+$(LIBDIR)/dev/libddlo_gicp.so: $(SRCS:%=$(LIBDIR)/dev/%.o)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
+dev: $(LIBDIR)/dev/libddlo_gicp.so
 .PHONY: dev
+-include $(SRCS:%=$(LIBDIR)/dev/%.d)

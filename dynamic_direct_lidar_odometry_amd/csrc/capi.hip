@@ -136,8 +136,8 @@ static gicp_status check_option(int option, int value) {
 // The search's development knobs, read from the environment once per
 // process, not on every align (host time between aligns).
 struct SearchKnobs {
-  float split_extent, hard_extent, probe, probe_d, tri_mv, reuse_gap, reuse_gap0, reuse_rec_eps, reuse_rec_conv;
-  int xcd_scan, pf_ratio, hard_blocks, prev_window, reuse, reuse_rec0, tie_scan, tie_ab;
+  float split_extent, probe, probe_d, tri_mv, reuse_gap, reuse_gap0, reuse_rec_eps, reuse_rec_conv;
+  int xcd_scan, pf_ratio, prev_window, reuse, reuse_rec0, tie_scan, tie_ab;
 };
 const SearchKnobs& search_knobs() {
   static const SearchKnobs k = [] {
@@ -145,8 +145,6 @@ const SearchKnobs& search_knobs() {
     v.split_extent = env_float("DDLO_SPLIT_EXTENT", kSplitExtentDefault);
     v.xcd_scan = env_int("DDLO_XCD_SCAN", 1);
     v.pf_ratio = env_int("DDLO_PF_RATIO", 2);
-    v.hard_extent = env_float("DDLO_HARD_EXTENT", 4.0f);
-    v.hard_blocks = env_int("DDLO_HARD_BLOCKS", 10);
     v.prev_window = env_int("DDLO_PREV_WINDOW", 2);
     v.tri_mv = env_float("DDLO_TRI_MV", 0.2f);
     v.probe = env_float("DDLO_PROBE", 1.0f);
@@ -166,7 +164,7 @@ const SearchKnobs& search_knobs() {
 
 // byte layout of ctx->search for ns source points
 struct SearchLayout {
-  size_t qstate, key, ctr, hard_list, hard_flag, grp_blocks, ref, ref_p, sec, key2, tasks, total;
+  size_t qstate, key, ctr, ref, ref_p, sec, key2, tasks, total;
   int cap_r;
   explicit SearchLayout(int ns) {
     auto al = [](size_t b) { return (b + 255) / 256 * 256; };
@@ -174,10 +172,7 @@ struct SearchLayout {
     qstate = 0;
     key = al(sizeof(float4) * (size_t)ns);
     ctr = key + al(sizeof(unsigned long long) * (size_t)ns);
-    hard_list = ctr + al(sizeof(unsigned) * (kTaskCounters + 1) * kCtrStride);   // + the moment kernel's arrival counter
-    hard_flag = hard_list + al(sizeof(int) * kHardMax);
-    grp_blocks = hard_flag + al((size_t)ns / 16 + 16);
-    ref = grp_blocks + al(sizeof(unsigned short) * ((size_t)ns / 16 + 16));
+    ref = ctr + al(sizeof(unsigned) * (kTaskRegions + 1) * kCtrStride);   // + the moment kernel's arrival counter
     ref_p = ref + al(sizeof(float4) * (size_t)ns);
     sec = ref_p + al(sizeof(float4) * (size_t)ns);
     key2 = sec + al(sizeof(unsigned) * (size_t)ns);
@@ -615,9 +610,6 @@ gicp_status fill_job(gicp_ctx* c, const float* guess16, int nblocks) {
     j.task_ctr = reinterpret_cast<unsigned*>(u + sl.ctr);
     j.tasks = reinterpret_cast<unsigned long long*>(u + sl.tasks);
     j.task_cap_r = sl.cap_r;
-    j.hard_list = reinterpret_cast<int*>(u + sl.hard_list);
-    j.hard_flag = reinterpret_cast<unsigned char*>(u + sl.hard_flag);
-    j.grp_blocks = reinterpret_cast<unsigned short*>(u + sl.grp_blocks);
     j.ref = reinterpret_cast<float4*>(u + sl.ref);
     j.ref_p = reinterpret_cast<float4*>(u + sl.ref_p);
     j.sec = reinterpret_cast<unsigned*>(u + sl.sec);
@@ -625,8 +617,6 @@ gicp_status fill_job(gicp_ctx* c, const float* guess16, int nblocks) {
   }
   j.xcd_scan = kn.xcd_scan;
   j.pf_ratio = kn.pf_ratio;
-  j.hard_extent = kn.hard_extent;
-  j.hard_blocks = kn.hard_blocks;
   j.prev_window = kn.prev_window;
   j.tri_mv = kn.tri_mv;
   j.probe2 = kn.probe * kn.probe;
@@ -827,7 +817,7 @@ void drop_graphs(gicp_ctx* c) {
 // single-iteration graphs now, first chunks on demand), evicting the least
 // recently used set -- after the stream's queued chunk, which may be one of
 // its graphs, has run.
-gicp_status graph_set(gicp_ctx* c, const std::array<long long, 8>& key, int nblocks, GraphSet** out);
+gicp_status graph_set(gicp_ctx* c, const std::array<long long, 7>& key, int nblocks, GraphSet** out);
 
 // Launch the align as a first chunk of n outer iterations (n = the previous
 // align's iteration count on this ctx: aligns of consecutive scans converge
@@ -843,9 +833,8 @@ gicp_status run_align_graph(gicp_ctx* c, int max_it, int nblocks, int* final_chu
   const LinGeom g = geometry(c);
   (void)nblocks;   // = g.mom_blocks
   // (the slab buffer: k_lm_step takes it as an argument; pool blocks are 256-B aligned, bit 0 = RCCL)
-  const std::array<long long, 8> key{{(long long)(uintptr_t)c->slab.p | (c->comm ? 1 : 0), (long long)(uintptr_t)jd,
-                                      g.seed_blocks, g.collect_blocks,
-                                      g.scan_blocks, g.mom_blocks, g.lds_boxes,
+  const std::array<long long, 7> key{{(long long)(uintptr_t)c->slab.p | (c->comm ? 1 : 0), (long long)(uintptr_t)jd,
+                                      g.seed_blocks, g.scan_blocks, g.mom_blocks, g.lds_boxes,
                                       g.grid ? (g.grid_walk ? 2L : 1L) * g.lookup_blocks : 0}};
   const bool use_graph = !c->comm || c->comm_graphs;
   const int first = c->params.fixed_iterations > 0
@@ -966,7 +955,7 @@ gicp_status run_align_graph(gicp_ctx* c, int max_it, int nblocks, int* final_chu
   return GICP_OK;
 }
 
-gicp_status graph_set(gicp_ctx* c, const std::array<long long, 8>& key, int nblocks, GraphSet** out) {
+gicp_status graph_set(gicp_ctx* c, const std::array<long long, 7>& key, int nblocks, GraphSet** out) {
   ++c->graph_clock;
   for (auto& gs : c->gsets)
     if (gs.key == key) {

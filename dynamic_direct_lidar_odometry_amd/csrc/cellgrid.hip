@@ -9,7 +9,7 @@
 //   K7a k_cg_occ / k_cg_dilate x3 / k_cg_band: coarse cells within reach of
 //       the target (Chebyshev dilation of the occupied cells by the bound);
 //   K7b the exact nearest target point of each band cell's centre
-//       (k_knn_query, kernels.hip);
+//       (k_knn_query, covariance.hip);
 //   K7c k_cg_coarse: one wavefront per band cell walks the Morton hierarchy
 //       for the points within the cell's reach, keeps those the centre's
 //       nearest point does not dominate, finds the corners' nearest points
@@ -20,7 +20,7 @@
 //       the children's dominators are found in it);
 //   K7e k_cg_emit_count / k_cg_emit_write: the final level of every coarse
 //       cell written as a fine table and point copies (x, y, z, position).
-// Lookup: k_cell_lookup (kernels.hip), one query per lane.
+// Lookup: k_cell_lookup (corr_search.hip), one query per lane.
 #include <hip/hip_runtime.h>
 
 #include "cellgrid.hpp"

@@ -35,11 +35,10 @@ constexpr int kStatFields = 8;    // per-wave diagnostic counters (DDLO_STATS)
 
 // Task list of the correspondence search (nn_tasks.hpp): kTaskRegions
 // append counters, kCtrStride words apart (one 128-B line each), and
-// kTasksPerGroup task slots per 16-query sub-group on average.
+// kTasksPerGroup task slots per 16-query sub-group on average.  One more
+// counter word follows the regions': the moment kernel's arrival counter.
 constexpr int kTaskRegions = 64;
-constexpr int kTaskCounters = kTaskRegions + 1;   // + the hard sub-group list's length
 constexpr int kCtrStride = 32;
-constexpr int kHardMax = 1024;    // hard sub-groups walked first (longest walks first)
 constexpr int kTasksPerGroup = 48;
 
 struct CloudDev {
@@ -222,14 +221,9 @@ struct AlignJob {
   float4* qstate;                // [n_src] transformed query (x, y, z) + seed bound (< 0: inactive)
   unsigned long long* key;       // [n_src] (squared distance, sorted target position) of the best match
   unsigned long long* tasks;     // [kTaskRegions][task_cap_r]
-  unsigned* task_ctr;            // [kTaskRegions * kCtrStride]
+  unsigned* task_ctr;            // [(kTaskRegions + 1) * kCtrStride]: + the moment kernel's arrival counter
   int task_cap_r;
-  int* hard_list;                // [kHardMax] sub-groups with a wide union box
-  unsigned char* hard_flag;      // [n_src / 16] 1 = listed (walked by the first waves)
-  float hard_extent;             // union-box extent (m) above which a sub-group is hard (first iteration)
-  unsigned short* grp_blocks;    // [n_src / 16] blocks the last collect walked per sub-group
-  int hard_blocks;               // later iterations: hard if the last walk took more blocks
-  int xcd_scan;                  // scan: one spatial eighth of the tasks per XCD (speed only)
+  int xcd_scan;            // scan: one spatial eighth of the tasks per XCD (speed only)
   int pf_ratio;                  // collect: lane-per-leaf pair tests below this queries / leaf-rounds ratio (speed only)
   int prev_window;         // seed after a large pose step: 0 previous match only, 1 + Morton window around it,
                            // 2 + Morton window at the new position (default)

@@ -4,7 +4,7 @@
 // KNNResultSet semantics, nanoflann_impl.hpp:161-242, with the sorted
 // position breaking exact distance ties).
 //
-// The lane-per-query traversal (kernels.hip k_covariances) lasts as long as
+// The lane-per-query traversal (covariance.hip k_covariances) lasts as long as
 // its slowest wavefront: a sparse far-range point whose k-th neighbour is
 // metres away walks and scans hundreds of leaves alone.  Here that work is
 // spread over the chip as tasks, like the correspondence search

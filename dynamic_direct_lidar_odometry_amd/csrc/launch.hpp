@@ -1,5 +1,6 @@
-// launch.hpp — host-callable launchers of the kernels in kernels.hip.  The
-// host runtime (capi.hip) only sees these plain functions.
+// launch.hpp — host-callable launchers of the kernels in the stage files
+// (index_build, covariance, corr_search, moments, outputs .hip) and the other
+// translation units.  The host runtime (capi.hip) only sees these plain functions.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -52,7 +53,7 @@ void launch_align_init(hipStream_t s, AlignJob* job, const AlignJob* job_src);
 // Launch geometry of one linearize (grids, upper-box LDS cache), bucketed by
 // cloud size; part of the chunk-graph key.
 struct LinGeom {
-  int seed_blocks, collect_blocks, scan_blocks, mom_blocks, lds_boxes, lookup_blocks;
+  int seed_blocks, scan_blocks, mom_blocks, lds_boxes, lookup_blocks;
   bool fuse_lm = false;   // the LM step runs in the moment kernel's last block (no k_lm_step launch)
   AlignState* state = nullptr;   // the job's state (job->state), a kernel argument of the moment kernel
   bool grid = false;      // the target's candidate cells answer the search first (k_cell_lookup)

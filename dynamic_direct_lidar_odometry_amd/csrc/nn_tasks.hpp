@@ -5,7 +5,7 @@
 //
 // Two kernels per outer iteration, both latency-tolerant and load-balanced:
 //
-//   k_nn_collect   one wavefront per 16 Morton-consecutive source points
+//   k_nn_seed      one wavefront per 16 Morton-consecutive source points
 //                  (a sub-group): transform, seed an exact upper bound
 //                  (previous match / Morton window / neighbours' points),
 //                  walk the LDS-cached upper levels with the union box of the

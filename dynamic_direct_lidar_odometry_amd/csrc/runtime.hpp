@@ -308,7 +308,7 @@ struct hipExecGraphPair {
 // publishing to state slot s = 0, 1; captured for: RCCL in the chunk, job
 // buffer, launch geometry (LinGeom).
 struct GraphSet {
-  std::array<long long, 8> key{{-1, -1, -1, -1, -1, -1, -1, -1}};
+  std::array<long long, 7> key{{-1, -1, -1, -1, -1, -1, -1}};
   std::vector<hipExecGraphPair> first;
   hipExecGraphPair rest[2];
   long long last_use = 0;
