@@ -520,8 +520,14 @@ gicp_status ensure_tmp(ddlo_odom* o, int n) {
   return GICP_OK;
 }
 
-// crop box + voxel filter of the float4 points in o->a (n) -> o->a; returns count
-gicp_status preprocess(ddlo_odom* o, int n, bool crop, double crop_size, bool vox, double leaf, int* nout) {
+// crop box + voxel filter of the float4 points in o->a (n) -> o->a; returns count.
+// *finite_out (optional): the output is known finite, i.e. a crop pass ran (it
+// drops non-finite points) or a voxel pass produced centroids (or nothing is
+// left).  Not so when neither filter is on, or when the voxel grid overflowed
+// with no crop box: the input is then passed on as it came, NaN points included.
+gicp_status preprocess(ddlo_odom* o, int n, bool crop, double crop_size, bool vox, double leaf, int* nout,
+                       bool* finite_out = nullptr) {
+  if (finite_out) *finite_out = false;
   HIP_TRY(o->b.ensure(sizeof(float4) * (size_t)std::max(n, 1)));
   HIP_TRY(o->keep.ensure(sizeof(int) * (size_t)std::max(n, 1)));
   HIP_TRY(o->pos.ensure(sizeof(int) * (size_t)std::max(n, 1)));
@@ -541,12 +547,15 @@ gicp_status preprocess(ddlo_odom* o, int n, bool crop, double crop_size, bool vo
       std::swap(o->a.p, o->b.p);
       std::swap(o->a.bytes, o->b.bytes);
       HIP_TRY(hipGetLastError());
+      if (finite_out) *finite_out = true;
       return GICP_OK;
     }
     // grid overflow: the reference keeps the cropped cloud unchanged -> crop alone below
     vox = false;
   }
+  bool finite = m <= 0;
   if (crop && m > 0) {
+    finite = true;
     if (crop_box(o->s, o->a.as<float4>(), m, (float)crop_size, o->b.as<float4>(), o->keep.as<int>(), o->pos.as<int>(),
                  o->cubtmp.p, o->cubtmp.bytes, &m, o->count_pin))
       return fail(GICP_EHIP, "crop box scratch too small");
@@ -559,6 +568,7 @@ gicp_status preprocess(ddlo_odom* o, int n, bool crop, double crop_size, bool vo
                    o->cubtmp.bytes, &c, 0.f, o->count_pin))
       return fail(GICP_EHIP, "voxel filter scratch too small");
     if (c >= 0) {  // -1: grid overflow, the reference keeps the cloud unchanged
+      finite = true;
       m = c;
       std::swap(o->a.p, o->b.p);
       std::swap(o->a.bytes, o->b.bytes);
@@ -566,11 +576,12 @@ gicp_status preprocess(ddlo_odom* o, int n, bool crop, double crop_size, bool vo
   }
   HIP_TRY(hipGetLastError());
   *nout = m;
+  if (finite_out) *finite_out = finite;
   return GICP_OK;
 }
 
-// device cloud from float4 points; `finite`: the points are known finite (a
-// voxel filter's output, keyframes, the submap), no read-back of the check
+// device cloud from float4 points; `finite`: the points are known finite
+// (preprocess() says so for a scan; keyframes, the submap), no read-back of the check
 // with_cov: covariances follow (the scan, a keyframe), so nanoflann's tree
 // for their tie order starts with the index build (not for the submap,
 // whose covariances are the keyframes')
@@ -595,6 +606,10 @@ gicp_status make_keyframe_from_a(ddlo_odom* o, int n) {
   kf->n = m;
   HIP_TRY(kf->pts.ensure(sizeof(float4) * (size_t)m));
   HIP_TRY(hipMemcpyAsync(kf->pts.p, o->a.p, sizeof(float4) * (size_t)m, hipMemcpyDeviceToDevice, o->s));
+  // finite whatever preprocess() did (a grid overflow passes the input on):
+  // the input is a scan cloud that passed cloud_from's check, transformed by
+  // the pose, or seg_static_cloud_dev's output, which drops non-finite points
+  // in its crop / voxel pass
   Side side;
   st = cloud_from(o, o->s2s, kf->pts.as<float4>(), m, &side.cloud, true, true);
   if (st) return st;
@@ -909,7 +924,8 @@ static gicp_status process_scan(ddlo_odom* o, const float* xyz, size_t n, size_t
   launch_pack4(o->s, o->up.as<unsigned char>(), stride, N, o->a.as<float4>());
   mark(0);
   int m = N;
-  st = preprocess(o, N, o->p.crop_use != 0, o->p.crop_size, o->p.vf_scan_use != 0, o->p.vf_scan_res, &m);
+  bool scan_finite = false;
+  st = preprocess(o, N, o->p.crop_use != 0, o->p.crop_size, o->p.vf_scan_use != 0, o->p.vf_scan_res, &m, &scan_finite);
   if (st) return st;
   res->scan_points = m;
   mark(1);
@@ -956,9 +972,10 @@ static gicp_status process_scan(ddlo_odom* o, const float* xyz, size_t n, size_t
     metrics();
     return fail(GICP_ETOOFEW, "preprocessed scan has fewer points than k_correspondences");
   }
-  // the preprocessed scan as a device cloud (finite after the voxel filter)
+  // the preprocessed scan as a device cloud (checked for non-finite points
+  // unless the preprocessing is known to have dropped them)
   std::shared_ptr<CloudData> scan;
-  st = cloud_from(o, o->s2s, o->a.as<float4>(), m, &scan, o->p.vf_scan_use != 0, true);
+  st = cloud_from(o, o->s2s, o->a.as<float4>(), m, &scan, scan_finite, true);
   if (st) return st;
   mark(2);
 
@@ -1165,6 +1182,31 @@ gicp_status ddlo_preprocess(int device, const float* xyz, size_t n, size_t strid
       out[3 * i + 2] = h[i].z;
     }
   }
+  return GICP_OK;
+}
+
+gicp_status ddlo_median_range(int device, const float* xyz, size_t n, size_t stride, float* median) {
+  if ((!xyz && n) || !median || stride < 12 || stride % 4 || n > (size_t)INT32_MAX / 2) return fail(GICP_EINVAL, "invalid argument");
+  ddlo_odom_params p;
+  ddlo_odom_default_params(&p);
+  ddlo_odom* o = nullptr;
+  gicp_status st = ddlo_odom_create(device, &p, &o);
+  if (st) return st;
+  std::unique_ptr<ddlo_odom, gicp_status (*)(ddlo_odom*)> guard(o, ddlo_odom_destroy);
+  *median = 0.f;
+  if (n == 0) return GICP_OK;
+  HIP_TRY(o->up.ensure((n - 1) * stride + 12));
+  HIP_TRY(hipMemcpyAsync(o->up.p, xyz, (n - 1) * stride + 12, hipMemcpyHostToDevice, o->s));
+  HIP_TRY(o->a.ensure(sizeof(float4) * n));
+  launch_pack4(o->s, o->up.as<unsigned char>(), stride, (int)n, o->a.as<float4>());
+  HIP_TRY(o->rng.ensure(sizeof(float) * n));
+  HIP_TRY(o->rng_sorted.ensure(sizeof(float) * n));
+  HIP_TRY(o->medtmp.ensure(median_tmp_bytes((int)n)));
+  median_range_async(o->s, o->a.as<float4>(), (int)n, o->rng.as<float>(), o->rng_sorted.as<float>(), o->medtmp.p,
+                     o->medtmp.bytes, o->median_pin);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(o->s));
+  *median = *o->median_pin;
   return GICP_OK;
 }
 

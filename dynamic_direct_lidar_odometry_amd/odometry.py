@@ -16,7 +16,7 @@ from . import GicpError, GicpParams, GicpResult, _ptr, load
 from .segmentation import OBJECT_DTYPE, SegObject, SegResult, Segmentation
 
 __all__ = ["OdomParams", "OdomResult", "DynamicParams", "NONSTATIC_FN", "Odometry", "default_odom_params",
-           "default_dynamic_params", "preprocess", "convex_hull", "concave_hull", "TRACKED", "FIRST", "SKIPPED", "INIT"]
+           "default_dynamic_params", "preprocess", "median_range", "convex_hull", "concave_hull", "TRACKED", "FIRST", "SKIPPED", "INIT"]
 
 TRACKED, FIRST, SKIPPED, INIT = 0, 1, 2, 3
 
@@ -95,6 +95,7 @@ def _lib():
             "ddlo_odom_submap": (I, [P, P, S, C.POINTER(S)]),
             "ddlo_odom_ctx": (I, [P, I, C.POINTER(P)]),
             "ddlo_preprocess": (I, [I, P, S, S, D, D, P, S, C.POINTER(S)]),
+            "ddlo_median_range": (I, [I, P, S, S, C.POINTER(C.c_float)]),
             "ddlo_convex_hull": (I, [P, I, P, I, C.POINTER(I)]),
             "ddlo_concave_hull": (I, [P, I, D, P, I, C.POINTER(I)]),
         }
@@ -227,6 +228,20 @@ def preprocess(points, crop_size: float = 0.0, leaf: float = 0.0, device: int = 
     _check(_lib().ddlo_preprocess(device, _ptr(a), a.shape[0], 12, float(crop_size), float(leaf), _ptr(out),
                                   out.shape[0], C.byref(n)))
     return out[:n.value]
+
+
+def median_range(points, stride: int = 12, device: int = 0) -> float:
+    """Element n // 2 of the sorted ranges of the points (the spaciousness metric's median), no preprocessing.
+    stride 12: anything that reshapes to (n, 3); else a float32 array of (n, stride // 4) columns, xyz first."""
+    if stride == 12:
+        a = _xyz(points)
+    else:
+        a = np.ascontiguousarray(points, np.float32)
+        if a.ndim != 2 or a.shape[1] * 4 != stride:
+            raise ValueError("points must be (n, stride // 4) float32")
+    m = C.c_float()
+    _check(_lib().ddlo_median_range(device, _ptr(a), a.shape[0], stride, C.byref(m)))
+    return np.float32(m.value)
 
 
 def convex_hull(points) -> np.ndarray:

@@ -140,6 +140,11 @@ gicp_status ddlo_odom_ctx(struct ddlo_odom* o, int which, struct gicp_ctx** ctx)
  * of out in points). */
 gicp_status ddlo_preprocess(int device, const float* xyz, size_t n, size_t stride_bytes, double crop_size, double leaf,
                             float* out, size_t cap, size_t* nout);
+/* The median range behind the spaciousness metric on its own (computeSpaciousness,
+ * odom.cc:981-1001): element n / 2 of the sorted ranges float(sqrt(x^2 + y^2 +
+ * z^2)) of the n points as they are, with no preprocessing; n == 0 gives 0.
+ * Exposed for the tests. */
+gicp_status ddlo_median_range(int device, const float* xyz, size_t n, size_t stride_bytes, float* median);
 
 /* Hull keyframe selection (OdomNode::computeConvexHull / computeConcaveHull,
  * odom.cc:1003-1065, pcl::ConvexHull / pcl::ConcaveHull with setDimension(3),

@@ -30,7 +30,8 @@ def declared():
 
 def test_odom_symbols_exported_and_bound():
     names = declared()
-    assert {"ddlo_odom_create", "ddlo_odom_process", "ddlo_odom_destroy", "ddlo_preprocess"} <= set(names)
+    assert {"ddlo_odom_create", "ddlo_odom_process", "ddlo_odom_destroy", "ddlo_preprocess",
+            "ddlo_median_range"} <= set(names)
     out = subprocess.run(["nm", "-D", "--defined-only", P.lib_path()], check=True, capture_output=True, text=True).stdout
     exported = {l.split()[-1] for l in out.splitlines() if l.strip()}
     assert not [n for n in names if n not in exported]
