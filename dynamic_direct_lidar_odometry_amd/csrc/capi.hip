@@ -870,7 +870,8 @@ gicp_status run_align_graph(gicp_ctx* c, int max_it, int nblocks, int* final_chu
   const int nchunks = 1 + (max_it - first);
   while ((int)c->chunk_ev.size() < nchunks) {
     hipEvent_t e;
-    HIP_TRY(hipEventCreate(&e));  // timed: the last one ends the align's device time
+    // (untimed: only profiled aligns take a device time, from events of their own)
+    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     c->chunk_ev.push_back(e);
   }
   gicp_status s = launch_chunk(0);
@@ -1305,7 +1306,7 @@ gicp_status gicp_align(gicp_ctx* c, const float* guess16, float* out16, gicp_res
     JobCommit commit(c);
     const int max_it = c->job_host->max_iterations;
     end_ev = c->ev1;
-    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    if (c->profiling) HIP_TRY(hipEventRecord(c->ev0, c->stream));   // (read only by the profiled path below)
     if (c->profiling || max_it <= 0) {
       s = max_it > 0 ? run_align_eager_profiled(c, max_it, nblocks) : GICP_OK;
       if (s) return s;

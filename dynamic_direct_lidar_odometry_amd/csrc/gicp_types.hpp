@@ -167,8 +167,8 @@ struct AlignState {
   int ties_resolved;     // tied queries re-run through the target's nanoflann tree (this align)
   int tie_err;           // a re-run failed (bits as k_nf_resolve_*: 1 depth, 2 tree build, 16 distance mismatch)
   // publication word (pinned copies only; 0 in the device state): k_lm_step
-  // writes (ticket << 17 | done << 16 | iter) after the rest of the copy and a
-  // system-scope fence, so the host that sees its align's ticket and the
+  // writes (ticket << 17 | done << 16 | iter) after the rest of the copy with a
+  // system-scope release (publish_state), so the host that sees its align's ticket and the
   // chunk's iteration reads a complete state without waiting on a HIP event
   unsigned long long pub;
 };

@@ -160,7 +160,7 @@ __device__ __forceinline__ void resolve_tied_corr(const AlignJob* __restrict__ j
   const int lane = lane_id();
   const NfTreeDev t = job->tgt_nf;
   if (t.nodes == nullptr) {
-    if (lane == __builtin_ctzll(tm)) st->tie_pending = 1;
+    if (lane == __builtin_ctzll(tm)) atomicOr(&st->tie_pending, 1);   // (an atomic: the last block may publish it in this launch)
     return;
   }
   if (*job->tgt_nf_status) {   // the tree build failed: keep the Morton-order answers, report
@@ -201,6 +201,10 @@ __device__ __forceinline__ void resolve_tied_corr(const AlignJob* __restrict__ j
 // an arrival counter (memory-side atomic); the block that arrives last takes
 // one agent-scope acquire and reads the slab with plain loads
 // (MI355X_MICROARCH.md "visibility", the split-K form of Guideline 16).
+// Measured and not kept (DESIGN.md §4 "LM step", round 7): sc1 buffer loads
+// of the slab in place of the acquire, with a counter that is never re-armed
+// -- no gain on its own or on top of the fence-free publication below.
+// The last block then publishes the state itself (publish_state).
 // LOOKUP (candidate cells without any fallback cell): the correspondence
 // lookup of k_cell_lookup is done here, one query per lane, and the match's
 // coordinates come from its list entry -- no lookup kernel, no key / sec
@@ -227,23 +231,84 @@ __device__ unsigned long long g_mom_prof[kMomProfIters * kMomProfWaves * 6];   /
 #else
 #define MOM_PROF(i)
 #endif
+// The three tie words of the state are written by whichever block meets a
+// tie (resolve_tied_corr: agent-scope atomics), possibly in the launch that
+// publishes them: the publishing block's one lane kTieThread fetches them
+// with returning agent-scope atomics, which are performed where the other
+// blocks' were.  In the fused kernel only after the arrival count has shown
+// every block done (each block's waves drain vmcnt before the add).
+struct TieWords {
+  int pending, resolved, err;
+};
+constexpr int kTieThread = 64 * (kMomWaves - 1);   // lane 0 of the last wave: idle through the LM step's serial part
+__device__ __forceinline__ TieWords fetch_tie_words(AlignState* st) {
+  // compare-and-swap of 0 for 0: changes nothing and returns the word.  (An
+  // or / add of a constant 0 is compiled to a load, and of an opaque 0 to
+  // three wave-reduced atomics, each waited for in turn; these three are
+  // issued back to back and waited for with the caller's next loads.)
+  TieWords tw{0, 0, 0};
+  __hip_atomic_compare_exchange_strong(&st->tie_pending, &tw.pending, 0, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_compare_exchange_strong(&st->ties_resolved, &tw.resolved, 0, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_compare_exchange_strong(&st->tie_err, &tw.err, 0, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+  return tw;
+}
+
 // Copy the state to the host-mapped slot, then its publication word
-// (AlignState::pub: ticket, done, iter) after a system-scope fence, so the
-// host that sees the word reads a complete state.  Whole block.
-__device__ __forceinline__ void publish_state(const AlignJob* __restrict__ job, const AlignState* __restrict__ st,
-                                              AlignState* __restrict__ publish) {
-  static_assert(sizeof(AlignState) % 16 == 0, "AlignState is copied in 16-byte words");
+// (AlignState::pub: ticket, done, iter), so the host that sees the word reads
+// a complete state.  Whole block (64 * kMomWaves threads); tw: thread
+// kTieThread's fetch_tie_words.  No thread takes a full fence:
+//   1. every wave drains its own stores to st (they are then in this XCD's
+//      L2: the L1 is write-through), one barrier;
+//   2. the copy reads st with 8-byte sc1 loads, which bypass this CU's L1 and
+//      are served by that L2 (a no-op iteration's or k_lm_step's unchanged
+//      words come from behind a kernel boundary either way);
+//   3. every storing wave drains its pinned stores, one barrier;
+//   4. thread 0's system-scope release store of the word, ordered behind the
+//      barrier, covers the block's stores.
+__device__ __forceinline__ void publish_state(const AlignJob* __restrict__ job, AlignState* __restrict__ st,
+                                              AlignState* __restrict__ publish, const TieWords& tw) {
+  static_assert(sizeof(AlignState) % 8 == 0, "AlignState is copied in 8-byte words");
   static_assert(offsetof(AlignState, pub) == sizeof(AlignState) - 8, "the publication word is the last 8 bytes");
-  __threadfence();   // this block's state stores, then an L1 invalidate before they are read back
+  static_assert(offsetof(AlignState, iter) % 8 == 0 && offsetof(AlignState, done) == offsetof(AlignState, iter) + 4,
+                "iter and done are one 8-byte word");
+  __shared__ int tie_s[3];
+  if (threadIdx.x == kTieThread) {
+    tie_s[0] = tw.pending;
+    tie_s[1] = tw.resolved;
+    tie_s[2] = tw.err;
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  const int4* src = reinterpret_cast<const int4*>(st);
-  int4* dst = reinterpret_cast<int4*>(publish);
-  for (int w = threadIdx.x; w < (int)(sizeof(AlignState) / 16); w += blockDim.x) dst[w] = src[w];
+  const auto src = gpw(reinterpret_cast<unsigned long long*>(st));
+  const auto dst = gpw(reinterpret_cast<unsigned long long*>(publish));
+  constexpr int kWords = (int)(sizeof(AlignState) / 8);
+  static_assert(kWords <= 64 * kMomWaves && kLmThreads == 64 * kMomWaves, "one 8-byte word per thread");
+  // an int of the state at byte offset off, within the 8-byte word w
+  auto patch = [](unsigned long long v, int w, size_t off, int val) {
+    if ((size_t)w != off / 8) return v;
+    const int sh = (int)(off & 4) * 8;
+    return (v & ~(0xffffffffull << sh)) | ((unsigned long long)(unsigned)val << sh);
+  };
+  // (iter, done) for the publication word, from the thread that copies them
+  __shared__ unsigned long long iter_s;
+  const int w = threadIdx.x;
+  if (w < kWords) {
+    unsigned long long v = __hip_atomic_load(src + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    v = patch(v, w, offsetof(AlignState, tie_pending), tie_s[0]);
+    v = patch(v, w, offsetof(AlignState, ties_resolved), tie_s[1]);
+    v = patch(v, w, offsetof(AlignState, tie_err), tie_s[2]);
+    dst[w] = v;
+    if (w == (int)(offsetof(AlignState, iter) / 8)) iter_s = v;
+  }
   const unsigned long long tk = job->ticket;
-  __threadfence_system();
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (threadIdx.x == 0) {
-    const unsigned long long w = (tk << 17) | ((unsigned long long)(st->done != 0) << 16) | ((unsigned)st->iter & 0xffffu);
+    const unsigned long long id = iter_s;
+    const unsigned long long w = (tk << 17) | ((unsigned long long)((unsigned)(id >> 32) != 0u) << 16) | (id & 0xffffu);
     __hip_atomic_store(&publish->pub, w, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
@@ -266,7 +331,11 @@ __global__ __launch_bounds__(64 * kMomWaves) void k_moments(const AlignJob* __re
   if (__builtin_amdgcn_readfirstlane(sg->done)) {
     // a no-op iteration after convergence: the chunk's publication still
     // happens (as k_lm_step's after an early exit), by block 0
-    if (FUSE_LM && publish && blockIdx.x == 0) publish_state(job, st, publish);
+    if (FUSE_LM && publish && blockIdx.x == 0) {
+      TieWords tw{};
+      if (threadIdx.x == kTieThread) tw = fetch_tie_words(st);
+      publish_state(job, st, publish, tw);
+    }
     return;
   }
   const CloudDev src = job->src;
@@ -539,8 +608,11 @@ __global__ __launch_bounds__(64 * kMomWaves) void k_moments(const AlignJob* __re
       atomicExch(arrive, 0u);   // re-armed for the next iteration (k_align_init zeroes it per align)
     }
     __syncthreads();
+    // every block has arrived, so the tie words are final: fetched in flight with the slab loads
+    TieWords tw{};
+    if (publish && threadIdx.x == kTieThread) tw = fetch_tie_words(st);
     lm_step_body<false>(job, st, job->slab, job->nblocks, nullptr);
-    if (publish) publish_state(job, st, publish);
+    if (publish) publish_state(job, st, publish, tw);
   }
 }
 template __global__ void k_moments<false>(const AlignJob*, AlignState*, AlignState*);
@@ -567,11 +639,13 @@ __global__ __launch_bounds__(kLmThreads) void k_lm_step(const AlignJob* __restri
                                                         const double* __restrict__ slab, int nblocks,
                                                         const double* __restrict__ premom,
                                                         AlignState* __restrict__ publish) {
+  TieWords tw{};
+  if (publish && threadIdx.x == kTieThread) tw = fetch_tie_words(st);
   if (!__builtin_amdgcn_readfirstlane(st->done)) {
     if (premom) lm_step_body<true>(job, st, slab, nblocks, premom);
     else lm_step_body<false>(job, st, slab, nblocks, nullptr);
   }
-  if (publish) publish_state(job, st, publish);
+  if (publish) publish_state(job, st, publish, tw);
 }
 
 void launch_linearize(hipStream_t s, const AlignJob* job, const LinGeom& g, AlignState* publish) {

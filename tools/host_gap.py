@@ -1,7 +1,12 @@
 """Developer timing: where a cfg 3 align's wall time goes on the host side.
-Per align: wall time of the C-ABI call (ctypes, cached pointers), the
-device span res.device_ms (event before the graph -> event after the final
-chunk) and their difference (host + launch latency)."""
+Wall time of the C-ABI call (ctypes, cached pointers) over graph aligns, the
+device span res.device_ms over profiled aligns of the same guess (only a
+profiled align takes one: event before its first kernel -> event after its
+last).  A profiled align runs eager with the LM step a kernel of its own, so
+its span holds the launch gaps of its 2 x iterations + 1 kernels (~0.5 ms at
+cfg 3) and is no part of a graph align's wall time: the two are printed side
+by side, not subtracted.  What a change to the host path buys shows in the
+call wall time of two builds (DDLO_GICP_LIB)."""
 import ctypes as C
 import os
 import sys
@@ -38,7 +43,12 @@ for i in range(N):
     t = time.perf_counter()
     f(c.h, gp, op, rp)
     wall[i] = time.perf_counter() - t
+c.set_profiling(True)
+for i in range(N):
+    f(c.h, gp, op, rp)
     dev[i] = res.device_ms
+c.set_profiling(False)
+f(c.h, gp, op, rp)
 t = time.perf_counter()
 for i in range(N):
     f(c.h, gp, op, rp)
@@ -50,6 +60,6 @@ loop_py = (time.perf_counter() - t) / N
 wall *= 1e6
 dev *= 1e3
 print(f"{os.environ.get('DDLO_GICP_LIB', 'lib')} spin={os.environ.get('DDLO_SPIN_WAIT', '0')}: "
-      f"call wall {np.median(wall):.1f} us (mean {wall.mean():.1f}), device span {np.median(dev):.1f} us, "
-      f"host+launch {np.median(wall - dev):.1f} us; back-to-back C-ABI {loop * 1e6:.1f} us/align, "
+      f"call wall {np.median(wall):.1f} us (mean {wall.mean():.1f}), profiled (eager) device span {np.median(dev):.1f} us; "
+      f"back-to-back C-ABI {loop * 1e6:.1f} us/align, "
       f"Context.align {loop_py * 1e6:.1f} us/align, iters {res.iterations_run}")
