@@ -80,6 +80,27 @@ class GicpResult(C.Structure):
     ]
 
 
+class GicpLmState(C.Structure):
+    """gicp_lm_state: the LM / GN step's state before and after gicp_debug_lm_step."""
+    _fields_ = [
+        ("R", C.c_double * 9),
+        ("t", C.c_double * 3),
+        ("lambda_", C.c_double),
+        ("final_cost", C.c_double),
+        ("final_hessian", C.c_double * 36),
+        ("last_b", C.c_double * 6),
+        ("last_mom", C.c_double * 80),
+        ("iter", C.c_int32),
+        ("lm_trials", C.c_int32),
+        ("converged", C.c_int32),
+        ("lm_failed", C.c_int32),
+        ("done", C.c_int32),
+        ("nr_iterations", C.c_int32),
+        ("num_corr", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 class GicpGridInfo(C.Structure):
     _fields_ = [
         ("built", C.c_int32),
@@ -164,6 +185,7 @@ def load():
         "gicp_linearize": (I, [P, P, P, P, P, P]),
         "gicp_knn_target": (I, [P, P, S, S, I, P, P]),
         "gicp_get_moments": (I, [P, P]),
+        "gicp_debug_lm_step": (I, [P, C.POINTER(GicpLmState), P, I, P, C.POINTER(GicpLmState)]),
         "gicp_set_profiling": (I, [P, I]),
         "gicp_debug_stats": (I, [P, I, P, S, C.POINTER(S)]),
         "gicp_get_stream": (I, [P, C.POINTER(P)]),
@@ -432,6 +454,24 @@ class Context:
     def moments(self):
         out = np.zeros(80)
         self._check(self.L.gicp_get_moments(self.h, _ptr(out)))
+        return out
+
+    def lm_step(self, R, t, lam=-1.0, it=0, lm_trials=0, slab=None, mom=None) -> GicpLmState:
+        """One LM / GN step on given moments (gicp_debug_lm_step; tests): slab = (nrows, 80) rows the
+        step sums itself, or mom = 80 reduced doubles.  Parameters are the context's."""
+        st = GicpLmState()
+        st.R[:] = np.asarray(R, np.float64).reshape(9)
+        st.t[:] = np.asarray(t, np.float64).reshape(3)
+        st.lambda_, st.iter, st.lm_trials = float(lam), int(it), int(lm_trials)
+        out = GicpLmState()
+        if slab is not None:
+            slab = np.ascontiguousarray(slab, np.float64)
+            slab = slab if slab.ndim == 2 and slab.shape[1] == 80 else slab.reshape(-1, 80)
+        if mom is not None:
+            mom = np.ascontiguousarray(mom, np.float64).reshape(80)
+        self._check(self.L.gicp_debug_lm_step(self.h, C.byref(st), None if slab is None else _ptr(slab),
+                                              0 if slab is None else len(slab), None if mom is None else _ptr(mom),
+                                              C.byref(out)))
         return out
 
     def knn_target(self, queries, k):

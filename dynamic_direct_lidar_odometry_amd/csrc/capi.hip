@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -1766,6 +1767,78 @@ gicp_status gicp_debug_nfbuild(gicp_ctx* c, int side, int stop, int32_t* vind, i
 gicp_status gicp_get_moments(const gicp_ctx* c, double* out80) {
   if (!c || !out80) return fail(GICP_EINVAL, "null argument");
   std::memcpy(out80, final_state(c).last_mom, sizeof(double) * kSlabStride);
+  return GICP_OK;
+}
+
+// One k_lm_step launch on given moments, on buffers of its own (tests): the
+// ctx lends its params, device and stream only.  The slab holds the step's
+// full 256 rows, NaN beyond the caller's, so a sum that reads a row at or
+// beyond nrows shows in the result; the step's clamped loads stay inside it.
+gicp_status gicp_debug_lm_step(gicp_ctx* c, const gicp_lm_state* in, const double* slab, int nrows, const double* mom80,
+                               gicp_lm_state* out) {
+  if (!c || !in || !out || !slab == !mom80) return fail(GICP_EINVAL, "null argument (pass either slab or mom80)");
+  const int max_rows = lm_slab_rows_max();
+  if (slab && (nrows < 1 || nrows > max_rows)) return fail(GICP_EINVAL, "nrows must be in [1, 256]");
+  gicp_status s = set_device(c);
+  if (s) return s;
+  AlignJob j{};
+  j.fixed_iterations = c->params.fixed_iterations;
+  j.max_iterations = c->params.fixed_iterations > 0 ? c->params.fixed_iterations : c->params.max_iterations;
+  j.optimizer = c->params.optimizer;
+  j.lm_max_iterations = c->params.lm_max_iterations;
+  j.lm_init_lambda_factor = c->params.lm_init_lambda_factor;
+  j.transformation_epsilon = c->params.transformation_epsilon;
+  j.rotation_epsilon = c->params.rotation_epsilon;
+  j.reuse = 0;
+  AlignState st{};
+  std::memcpy(st.R, in->R, sizeof(st.R));
+  std::memcpy(st.t, in->t, sizeof(st.t));
+  st.lambda = in->lambda;
+  st.final_cost = in->final_cost;
+  std::memcpy(st.final_hessian, in->final_hessian, sizeof(st.final_hessian));
+  std::memcpy(st.last_b, in->last_b, sizeof(st.last_b));
+  std::memcpy(st.last_mom, in->last_mom, sizeof(st.last_mom));
+  st.iter = in->iter;
+  st.lm_trials = in->lm_trials;
+  st.converged = in->converged;
+  st.lm_failed = in->lm_failed;
+  st.done = 0;   // (a finished state would make the kernel a no-op)
+  st.nr_iterations = in->nr_iterations;
+  st.num_corr = in->num_corr;
+  std::vector<double> rows;
+  if (slab) {
+    rows.assign((size_t)max_rows * kSlabStride, std::numeric_limits<double>::quiet_NaN());
+    std::memcpy(rows.data(), slab, sizeof(double) * (size_t)nrows * kSlabStride);
+  } else {
+    rows.assign(mom80, mom80 + kSlabStride);
+  }
+  DevBuf djob, dstate, dmom;
+  HIP_TRY(djob.ensure(sizeof(AlignJob)));
+  HIP_TRY(dstate.ensure(sizeof(AlignState)));
+  HIP_TRY(dmom.ensure(sizeof(double) * rows.size()));
+  HIP_TRY(hipMemcpyAsync(djob.p, &j, sizeof(j), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dstate.p, &st, sizeof(st), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(dmom.p, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice, c->stream));
+  launch_lm_step(c->stream, djob.as<AlignJob>(), dstate.as<AlignState>(), slab ? dmom.as<double>() : nullptr,
+                 slab ? nrows : 0, slab ? nullptr : dmom.as<double>(), nullptr);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(&st, dstate.p, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  std::memcpy(out->R, st.R, sizeof(st.R));
+  std::memcpy(out->t, st.t, sizeof(st.t));
+  out->lambda = st.lambda;
+  out->final_cost = st.final_cost;
+  std::memcpy(out->final_hessian, st.final_hessian, sizeof(st.final_hessian));
+  std::memcpy(out->last_b, st.last_b, sizeof(st.last_b));
+  std::memcpy(out->last_mom, st.last_mom, sizeof(st.last_mom));
+  out->iter = st.iter;
+  out->lm_trials = st.lm_trials;
+  out->converged = st.converged;
+  out->lm_failed = st.lm_failed;
+  out->done = st.done;
+  out->nr_iterations = st.nr_iterations;
+  out->num_corr = st.num_corr;
+  out->reserved = 0;
   return GICP_OK;
 }
 

@@ -66,6 +66,7 @@ void launch_linearize(hipStream_t s, const AlignJob* job, const LinGeom& g, Alig
 int search_queries_per_wave();
 int task_cap_per_region(int nsrc);   // task-list slots per region for nsrc source points
 int moment_blocks(int nsrc);  // slab rows written by the moment kernel
+int lm_slab_rows_max();       // the most slab rows one LM step reduces (kMomBlocksMax)
 // st / slab / nblocks / premom: the job's state, slab rows and (sharded) all-reduced moments, as
 // kernel arguments (the state and slab loads then need no job load first)
 void launch_lm_step(hipStream_t s, const AlignJob* job, AlignState* st, const double* slab, int nblocks,

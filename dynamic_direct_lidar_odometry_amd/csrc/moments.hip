@@ -666,6 +666,7 @@ int moment_blocks(int nsrc) {
   const int groups = (nsrc + 63) / 64;
   return std::max(1, std::min((groups + kMomWaves - 1) / kMomWaves, kMomBlocksMax));
 }
+int lm_slab_rows_max() { return kMomBlocksMax; }
 void launch_lm_step(hipStream_t s, const AlignJob* job, AlignState* st, const double* slab, int nblocks,
                     const double* premom, AlignState* publish) {
   k_lm_step<<<1, kLmThreads, 0, s>>>(job, st, slab, nblocks, premom, publish);

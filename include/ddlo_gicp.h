@@ -299,6 +299,36 @@ gicp_status gicp_debug_nfbuild(struct gicp_ctx* ctx, int side, int stop, int32_t
 /* The 74 reduced normal-equation moments of the last linearize (80 doubles,
  * layout in DESIGN.md "Normal-equation moments"); test/debug entry. */
 gicp_status gicp_get_moments(const struct gicp_ctx* ctx, double* out80);
+/* One LM / GN step (step_lm / step_gn, lsq_registration_impl.hpp:155-232) on
+ * given moments; test entry.  The step's state before and after: R, t,
+ * lambda (< 0: the first LM step), iter and lm_trials are its inputs; a field
+ * the step does not write keeps the value passed in. */
+typedef struct gicp_lm_state {
+  double R[9];               /* pose of the linearization -> the new pose, row-major */
+  double t[3];
+  double lambda;             /* lm_lambda_                                           */
+  double final_cost;         /* y0 (moment 72)                                       */
+  double final_hessian[36];  /* H, written by an accepted step only                  */
+  double last_b[6];          /* b                                                    */
+  double last_mom[80];       /* the reduced moments the step used                    */
+  int32_t iter;              /* outer iterations executed                            */
+  int32_t lm_trials;
+  int32_t converged;
+  int32_t lm_failed;
+  int32_t done;
+  int32_t nr_iterations;
+  int32_t num_corr;          /* moment 73                                            */
+  int32_t reserved;
+} gicp_lm_state;
+/* Runs the step kernel once, on scratch buffers of its own: the ctx needs no
+ * clouds and its align state is untouched.  The ctx's gicp_params give
+ * optimizer, lm_max_iterations, lm_init_lambda_factor, the two epsilons,
+ * max_iterations and fixed_iterations.  The moments come either as `slab`,
+ * nrows (1..256) rows of 80 doubles that the step sums in its fixed order
+ * (mom80 NULL), or as mom80, 80 doubles already reduced (slab NULL; the path
+ * of a sharded align).  Layout: DESIGN.md "Normal-equation moments". */
+gicp_status gicp_debug_lm_step(struct gicp_ctx* ctx, const gicp_lm_state* in, const double* slab, int nrows,
+                               const double* mom80, gicp_lm_state* out);
 /* Device time accounting of the linearize kernel inside align (HIP events
  * captured in the align graph).  Off by default. */
 gicp_status gicp_set_profiling(struct gicp_ctx* ctx, int enable);

@@ -8,11 +8,14 @@ Tolerances (floating point, stated per check):
   correspondences / sq. distances       bit-exact
   poses         |d| <= 1e-6             (fp32 output of an fp64 state)
   iterations / convergence flags        exact
+  lm_lambda     rel 16 x lm_ref.LAMBDA_SPREAD_REL (the float64 / longdouble spread of the reference's own
+                lm_lambda over whole aligns of the golden pair, measured in tests/test_lm_ref_cpu.py)
 """
 import numpy as np
 import pytest
 
 import dynamic_direct_lidar_odometry_amd as P
+import lm_ref as LR
 import np_gicp as NP
 from dynamic_direct_lidar_odometry_amd import SOURCE, TARGET
 from oracle import oracle as O
@@ -22,6 +25,16 @@ pytestmark = pytest.mark.gpu
 
 S2S = dict(k_correspondences=10, max_correspondence_distance=1.0, max_iterations=32, transformation_epsilon=5e-4)
 S2M = dict(k_correspondences=20, max_correspondence_distance=2.0, max_iterations=32, transformation_epsilon=0.01)
+
+
+def assert_lm_outcome(res, ores):
+    """lm_lambda, final_cost and nr_iterations of an align against the live oracle's."""
+    print(f"lm_lambda rel {abs(res.lm_lambda / ores.lm_lambda - 1):.3g}, final_cost rel "
+          f"{abs(res.final_cost / ores.final_cost - 1):.3g}")
+    assert res.nr_iterations == ores.nr_iterations
+    assert abs(res.final_cost - ores.final_cost) <= 1e-11 * abs(ores.final_cost)
+    assert abs(res.lm_lambda - ores.lm_lambda) <= 16 * LR.LAMBDA_SPREAD_REL * abs(ores.lm_lambda), \
+        f"lm_lambda {res.lm_lambda!r} vs {ores.lm_lambda!r}: rel {abs(res.lm_lambda / ores.lm_lambda - 1):.3g}"
 
 
 def s2s_ctx(g, **kw):
@@ -221,6 +234,7 @@ def test_align_with_guess_and_param_variants(s2s_golden):
         opose, ores = o.align(guess)
         assert (res.iterations_run, res.converged, res.lm_trials) == (ores.iterations_run, ores.converged, ores.lm_trials)
         np.testing.assert_allclose(pose, opose, atol=1e-6)
+        assert_lm_outcome(res, ores)
 
 
 def test_align_no_correspondences(s2s_golden):
@@ -236,6 +250,7 @@ def test_align_no_correspondences(s2s_golden):
     assert res.num_correspondences == 0
     assert (res.iterations_run, res.converged) == (ores.iterations_run, ores.converged)
     np.testing.assert_array_equal(pose, opose)
+    assert res.lm_lambda == ores.lm_lambda == 0.0   # lambda_0 = 1e-9 * max |diag 0|, times the NaN-rho factor 1/3
 
 
 def test_align_errors():
@@ -320,6 +335,7 @@ def test_align_sequence_on_one_ctx_matches_fresh_ctx(s2s_golden):
         np.testing.assert_array_equal(pose, fpose)
         assert (res.iterations_run, res.converged, res.lm_trials) == (ores.iterations_run, ores.converged, ores.lm_trials)
         np.testing.assert_allclose(pose, opose, atol=1e-6)
+        assert_lm_outcome(res, ores)
         # state read after the align (the trailing chunk may still be queued)
         out = c.transform_source()
         ref = (g["src"].astype(np.float64) @ pose[:3, :3].T.astype(np.float64) + pose[:3, 3]).astype(np.float32)
