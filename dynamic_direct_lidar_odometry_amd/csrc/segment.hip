@@ -15,11 +15,17 @@
 //                  receives the test(r + 1) write.  Each thread evaluates the
 //                  (at most two) tests that write its pixel: no column walk;
 //   label init     (:493-504): -1 for ground or no-range pixels, else 0.
-// Host: the labelling (cloudSegmentation / labelComponents, :510-724) is a
-// breadth-first search whose result depends on the visiting order (segment
-// numbers follow the row-major scan, min_z / max_z is an if / else-if over
-// the push order, the residual sum is a float sum in push order), so it runs
-// on the host as the north star places it, over the label image read back.
+// Labelling (cloudSegmentation / labelComponents, :510-724), two modes
+// (ddlo_seg_set_labelling):
+//   host (the default): the reference's breadth-first search, literally, over
+//     the images read back -- segment numbers follow the row-major scan,
+//     min_z / max_z is an if / else-if over the push order, the residual sum
+//     is a float sum in push order;
+//   device (seg_label.hip): the same labels and segment count without the
+//     search order (connected components, a replayed prefix for max_z); the
+//     average residuals are a double sum in row-major order, within
+//     (m + 1) 2^-24 of the host's float sum.  No image leaves the device
+//     unless a getter asks for it.
 //
 // Float behaviour follows the reference, where ddlo.h:35 includes <stdlib.h>
 // (libstdc++'s wrapper brings std::abs into the global namespace, <cmath>
@@ -38,6 +44,7 @@
 #include "launch.hpp"
 #include "runtime.hpp"
 #include "seg_internal.hpp"
+#include "seg_label.hpp"
 
 namespace ddlo {
 namespace {
@@ -138,11 +145,7 @@ struct Labeller {
   const float* resid;     // H x W or nullptr (icp_residuals_set_ false)
   int* label;             // H x W, in: -1 / 0
   float sin_x, cos_x, sin_y, cos_y, sensor_z;
-  // the angle test without atan2 away from the threshold: atan is monotonic,
-  // so for x > 0 the float atan2f(y, x) (within 1 ulp of atan(y / x)) is
-  // above theta when y / x > tan(theta (1 + 1e-6)) and not above it when
-  // y / x < tan(theta (1 - 1e-6)); in between (and for x <= 0) the
-  // reference's atan2 decides.  Same decisions, one division per edge.
+  // the angle test without atan2 away from the threshold (EdgeTrig, seg_label.hpp)
   double tan_lo = 0.0, tan_hi = 0.0;
   bool tan_ok = false;
   int label_count = 1;
@@ -161,20 +164,14 @@ struct Labeller {
       : p(p_), range(range_), z(z_), resid(resid_), label(label_), sensor_z(sensor_z_), avg_residual(avg), qy(w.qy),
         qx(w.qx), py(w.py), px(w.px), rows_hit(w.rows_hit), line_flag(w.line_flag), seg_off(w.seg_off), seg_pix(w.seg_pix) {
     const int H = p.rows, W = p.cols;
-    // loadParams :82-83,108-111: ang_res_x_ = 360.0 / float(W_) (double, stored
-    // as float), ang_res_y_ = 2 * ang_bottom_ / float(H_ - 1) (float); double sin/cos
-    const float ang_res_x = (float)(360.0 / (double)(float)W);
-    const float ang_res_y = 2.f * p.ang_bottom / (float)(H - 1);
-    sin_x = (float)std::sin(ang_res_x / 180.0 * M_PI);
-    cos_x = (float)std::cos(ang_res_x / 180.0 * M_PI);
-    sin_y = (float)std::sin(ang_res_y / 180.0 * M_PI);
-    cos_y = (float)std::cos(ang_res_y / 180.0 * M_PI);
-    const double th = (double)p.theta;
-    tan_ok = th > 1e-3 && th < 1.5;   // a threshold well inside (0, pi / 2): both bounds finite and ordered
-    if (tan_ok) {
-      tan_lo = std::tan(th * (1.0 - 1e-6));
-      tan_hi = std::tan(th * (1.0 + 1e-6));
-    }
+    const EdgeTrig t = edge_trig(p);   // (seg_label.hpp: shared with the device labelling)
+    sin_x = t.sin_x;
+    cos_x = t.cos_x;
+    sin_y = t.sin_y;
+    cos_y = t.cos_y;
+    tan_ok = t.tan_ok != 0;
+    tan_lo = t.tan_lo;
+    tan_hi = t.tan_hi;
     const size_t n = (size_t)H * W;
     if (qy.size() < n) {   // (grown once; every slot is written before it is read)
       qy.resize(n);
@@ -484,6 +481,28 @@ struct ObjStage {
   }
 };
 
+void launch_objects(hipStream_t s, const unsigned char* raw, size_t stride, const int* off, const int* pix, int L,
+                    DevBuf& dobj) {
+  SegObjArgs a{raw, stride, off, pix, dobj.as<ddlo_seg_object>()};
+  k_seg_objects<<<L, kObjThreads, 0, s>>>(a);
+}
+
+// the same over a CSR that is on the device already (the device labelling's)
+gicp_status run_objects_dev(hipStream_t s, const unsigned char* raw, size_t stride, const int* off, const int* pix,
+                            int L, DevBuf& dobj, std::vector<ddlo_seg_object>& recs, ObjStage& stage) {
+  recs.assign((size_t)L, ddlo_seg_object{});
+  if (L <= 0) return GICP_OK;
+  const size_t rec_b = sizeof(ddlo_seg_object) * (size_t)L;
+  HIP_TRY(dobj.ensure(rec_b));
+  if (gicp_status st = stage.ensure(rec_b)) return st;
+  launch_objects(s, raw, stride, off, pix, L, dobj);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(stage.p, dobj.p, rec_b, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  std::memcpy(recs.data(), stage.p, rec_b);
+  return GICP_OK;
+}
+
 // launch the object kernel for labels 1 .. L and read the records back
 // (stage: pinned staging, or nullptr for pageable copies)
 // off: L + 2 offsets, pix: off[L + 1] pixel indices (CSR, as ddlo_seg_label_indices)
@@ -511,8 +530,7 @@ gicp_status run_objects(hipStream_t s, const unsigned char* raw, size_t stride, 
   std::memcpy(rows_src, off.data(), sizeof(int) * noff);
   if (npix) std::memcpy(rows_src + noff, pix.data(), sizeof(int) * npix);
   HIP_TRY(hipMemcpyAsync(dcsr.p, rows_src, rows_b, hipMemcpyHostToDevice, s));
-  SegObjArgs a{raw, stride, dcsr.as<int>(), dcsr.as<int>() + noff, dobj.as<ddlo_seg_object>()};
-  k_seg_objects<<<L, kObjThreads, 0, s>>>(a);
+  launch_objects(s, raw, stride, dcsr.as<int>(), dcsr.as<int>() + noff, L, dobj);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(rec_dst, dobj.p, rec_b, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -521,6 +539,9 @@ gicp_status run_objects(hipStream_t s, const unsigned char* raw, size_t stride, 
 }
 
 }  // namespace
+
+gicp_status seg_check_params(const ddlo_seg_params* p) { return check_params(p); }
+
 }  // namespace ddlo
 
 using namespace ddlo;
@@ -552,7 +573,38 @@ struct ddlo_seg {
   LabelWork work;
   bool have = false;
   ddlo_seg_result last{};
+  // device labelling (ddlo_seg_set_labelling): its scratch and results, the
+  // residual image on the device, the pinned record read back per frame, and
+  // which host images (kImg*) the getters have fetched for the last scan
+  int labelling = DDLO_SEG_LABEL_HOST;
+  LabelDev ldev;
+  rt::DevBuf dresid, dids;
+  int* rec_pin = nullptr;
+  unsigned fetched = 0;
+  int replayed = 0, longest_prefix = 0;
 };
+
+// the pinned record: the ints and the first averages in one copy
+constexpr size_t kRecPinBytes = kLabelRecMinBytes;
+constexpr size_t kRecPinAvg = (kRecPinBytes - sizeof(int) * kLabelRecInts) / sizeof(double);
+enum : unsigned { kImgRange = 1, kImgGround = 2, kImgLabel = 4 };
+
+// device mode: the host images a getter needs, read back once per scan
+static gicp_status fetch_images(ddlo_seg* o, unsigned want) {
+  if (o->labelling != DDLO_SEG_LABEL_DEVICE) return GICP_OK;
+  const unsigned need = want & ~o->fetched;
+  if (!need) return GICP_OK;
+  const size_t n = o->hn;
+  HIP_TRY(hipSetDevice(o->device));
+  if (need & kImgRange)
+    HIP_TRY(hipMemcpyAsync(const_cast<float*>(o->h_range), o->range.p, sizeof(float) * n, hipMemcpyDeviceToHost, o->s));
+  if (need & kImgGround)
+    HIP_TRY(hipMemcpyAsync(const_cast<signed char*>(o->h_ground), o->ground.p, n, hipMemcpyDeviceToHost, o->s));
+  if (need & kImgLabel) HIP_TRY(hipMemcpyAsync(o->h_label, o->label.p, sizeof(int) * n, hipMemcpyDeviceToHost, o->s));
+  HIP_TRY(hipStreamSynchronize(o->s));
+  o->fetched |= need;
+  return GICP_OK;
+}
 
 extern "C" {
 
@@ -614,6 +666,7 @@ gicp_status ddlo_seg_destroy(ddlo_seg* s) {
   s->label.reset();
   if (s->pin) (void)hipHostFree(s->pin);
   if (s->cnt_pin) (void)hipHostFree(s->cnt_pin);
+  if (s->rec_pin) (void)hipHostFree(s->rec_pin);
   s->obj_stage.release();
   s->drop_stage.release();
   (void)hipStreamDestroy(s->s);
@@ -636,8 +689,9 @@ static gicp_status seg_run(ddlo_seg* o, const float* xyz_t, size_t stride, const
   HIP_TRY(o->range.ensure(sizeof(float) * n));
   HIP_TRY(o->ground.ensure(n));
   HIP_TRY(o->label.ensure(sizeof(int) * n));
+  const bool dev_label = o->labelling == DDLO_SEG_LABEL_DEVICE;
   if (xyz_t) HIP_TRY(hipMemcpyAsync(o->raw.p, xyz_t, raw_sz, hipMemcpyHostToDevice, o->s));
-  else HIP_TRY(o->zimg.ensure(sizeof(float) * n));
+  else if (!dev_label) HIP_TRY(o->zimg.ensure(sizeof(float) * n));
   SegPixelArgs a{};
   a.raw = o->raw.as<unsigned char>();
   a.stride = stride;
@@ -653,13 +707,51 @@ static gicp_status seg_run(ddlo_seg* o, const float* xyz_t, size_t stride, const
   a.range = o->range.as<float>();
   a.ground = o->ground.as<signed char>();
   a.label = o->label.as<int>();
-  a.zout = xyz_t ? nullptr : o->zimg.as<float>();
+  a.zout = (xyz_t || dev_label) ? nullptr : o->zimg.as<float>();
   k_seg_pixels<<<dim3(cdiv_s(W, 256), H), 256, 0, o->s>>>(a);
   HIP_TRY(hipGetLastError());
   float* pin_range = o->pin;
   int* pin_label = reinterpret_cast<int*>(o->pin + n);
   float* pin_z = reinterpret_cast<float*>(pin_label + n);
   signed char* pin_ground = reinterpret_cast<signed char*>(pin_z + n);
+  if (dev_label) {
+    // the labelling reads z from the scan itself; only the record comes back:
+    // the counts and the first averages, then the other averages if there are more
+    const float* dres = nullptr;
+    if (residual) {
+      HIP_TRY(rt::grow(o->dresid, sizeof(float) * n, o->s));
+      HIP_TRY(hipMemcpyAsync(o->dresid.p, residual, sizeof(float) * n, hipMemcpyHostToDevice, o->s));
+      dres = o->dresid.as<float>();
+    }
+    const LabelDevIn in{o->range.as<float>(), o->raw.as<unsigned char>() + 8, stride, dres, o->ground.as<signed char>(),
+                        o->label.as<int>(), T[11]};
+    if (gicp_status st = label_device_run(o->s, p, o->ldev, in)) return st;
+    HIP_TRY(hipMemcpyAsync(o->rec_pin, o->ldev.rec.p, kRecPinBytes, hipMemcpyDeviceToHost, o->s));
+    HIP_TRY(hipStreamSynchronize(o->s));
+    const int* ri = o->rec_pin;
+    if (ri[kRecError]) return fail(GICP_EHIP, "device labelling: a replay queue left its component's range");
+    const size_t navg = (size_t)ri[kRecSegments] + 1;
+    o->avg.assign(navg, 0.0);
+    const double* pavg = reinterpret_cast<const double*>(ri + kLabelRecInts);
+    for (size_t l = 0; l < navg && l < kRecPinAvg; ++l) o->avg[l] = pavg[l];
+    if (navg > kRecPinAvg) {
+      HIP_TRY(hipMemcpyAsync(o->avg.data() + kRecPinAvg, o->ldev.avg() + kRecPinAvg, sizeof(double) * (navg - kRecPinAvg),
+                             hipMemcpyDeviceToHost, o->s));
+      HIP_TRY(hipStreamSynchronize(o->s));
+    }
+    o->h_range = pin_range;
+    o->h_ground = pin_ground;
+    o->h_label = pin_label;
+    o->hn = n;
+    o->fetched = 0;
+    o->replayed = ri[kRecReplayed];
+    o->longest_prefix = ri[kRecLongestPrefix];
+    ddlo_seg_result r{ri[kRecSegments], ri[kRecGround], ri[kRecRange], ri[kRecRejected]};
+    o->last = r;
+    o->have = true;
+    if (res) *res = r;
+    return GICP_OK;
+  }
   HIP_TRY(hipMemcpyAsync(pin_range, o->range.p, sizeof(float) * n, hipMemcpyDeviceToHost, o->s));
   HIP_TRY(hipMemcpyAsync(pin_label, o->label.p, sizeof(int) * n, hipMemcpyDeviceToHost, o->s));
   HIP_TRY(hipMemcpyAsync(pin_ground, o->ground.p, n, hipMemcpyDeviceToHost, o->s));
@@ -703,6 +795,8 @@ gicp_status ddlo_seg_process(ddlo_seg* o, const float* xyz_t, size_t stride, con
 gicp_status ddlo_seg_images(ddlo_seg* o, float* range, int8_t* ground, int32_t* label) {
   if (!o) return fail(GICP_EINVAL, "null handle");
   if (!o->have) return fail(GICP_EINVAL, "no processed scan");
+  if (gicp_status st = fetch_images(o, (range ? kImgRange : 0u) | (ground ? kImgGround : 0u) | (label ? kImgLabel : 0u)))
+    return st;
   const size_t n = o->hn;
   if (range) std::memcpy(range, o->h_range, sizeof(float) * n);
   if (ground) std::memcpy(ground, o->h_ground, n);
@@ -721,6 +815,7 @@ gicp_status ddlo_seg_avg_residuals(ddlo_seg* o, double* out, size_t cap, size_t*
 gicp_status ddlo_seg_ground_indices(ddlo_seg* o, int32_t* out, size_t cap, size_t* n) {
   if (!o || !n || (!out && cap)) return fail(GICP_EINVAL, "invalid argument");
   if (!o->have) return fail(GICP_EINVAL, "no processed scan");
+  if (gicp_status st = fetch_images(o, kImgGround)) return st;
   const int H = o->p.rows, W = o->p.cols;
   size_t k = 0;
   for (int col = 0; col < W; ++col)
@@ -739,6 +834,7 @@ gicp_status ddlo_seg_label_indices(ddlo_seg* o, int32_t* offsets, size_t offsets
                                    size_t indices_cap, size_t* n_indices) {
   if (!o) return fail(GICP_EINVAL, "null handle");
   if (!o->have) return fail(GICP_EINVAL, "no processed scan");
+  if (gicp_status st = fetch_images(o, kImgLabel)) return st;
   const int L = o->last.segments;
   if (offsets && offsets_cap < (size_t)L + 2) return fail(GICP_EINVAL, "offsets needs segments + 2 entries");
   std::vector<int32_t> cnt(L + 2, 0);
@@ -808,7 +904,10 @@ gicp_status seg_objects_vec(ddlo_seg* o, float max_dim_ratio, std::vector<ddlo_s
   if (!o->have) return fail(GICP_EINVAL, "no processed scan");
   HIP_TRY(hipSetDevice(o->device));
   if (!o->have_objects) {
-    gicp_status st = run_objects(o->s, o->raw.as<unsigned char>(), o->raw_stride, o->work.seg_off, o->work.seg_pix,
+    gicp_status st = o->labelling == DDLO_SEG_LABEL_DEVICE
+                         ? run_objects_dev(o->s, o->raw.as<unsigned char>(), o->raw_stride, o->ldev.off(), o->ldev.pixels(),
+                                           o->last.segments, o->dobj, o->objects, o->obj_stage)
+                         : run_objects(o->s, o->raw.as<unsigned char>(), o->raw_stride, o->work.seg_off, o->work.seg_pix,
                                  o->last.segments, o->dcsr, o->dobj, o->objects, &o->obj_stage);
     if (st) return st;
     o->have_objects = true;
@@ -822,19 +921,26 @@ gicp_status seg_static_cloud_dev(ddlo_seg* o, const int32_t* remove_ids, size_t 
   if (!o || !pts || !count || !centre || (!remove_ids && n_remove)) return fail(GICP_EINVAL, "invalid argument");
   if (!o->have) return fail(GICP_EINVAL, "no processed scan");
   const int L = o->last.segments;
+  const bool dev_label = o->labelling == DDLO_SEG_LABEL_DEVICE;
   const std::vector<int>& off = o->work.seg_off;
   size_t ndrop = 0;
   for (size_t k = 0; k < n_remove; ++k) {
     if (remove_ids[k] < 1 || remove_ids[k] > L) return fail(GICP_EINVAL, "remove_ids names no segment of the last scan");
-    ndrop += (size_t)(off[remove_ids[k] + 1] - off[remove_ids[k]]);
+    if (!dev_label) ndrop += (size_t)(off[remove_ids[k] + 1] - off[remove_ids[k]]);
   }
   HIP_TRY(hipSetDevice(o->device));
   const int n = (int)o->hn;
-  // the removed segments' pixels (an id named twice is listed twice: harmless)
-  if (gicp_status st = o->drop_stage.ensure(sizeof(int) * std::max<size_t>(ndrop, 1))) return st;
+  // the removed segments' pixels (an id named twice is listed twice: harmless);
+  // device labelling: only their ids go up, the pixel lists are on the device
+  const size_t stage_ints = dev_label ? n_remove : ndrop;
+  if (gicp_status st = o->drop_stage.ensure(sizeof(int) * std::max<size_t>(stage_ints, 1))) return st;
   int* const drop = static_cast<int*>(o->drop_stage.p);
   size_t w = 0;
   for (size_t k = 0; k < n_remove; ++k) {
+    if (dev_label) {
+      drop[w++] = remove_ids[k];
+      continue;
+    }
     const int b = off[remove_ids[k]], e = off[remove_ids[k] + 1];
     std::memcpy(drop + w, o->work.seg_pix.data() + b, sizeof(int) * (size_t)(e - b));
     w += (size_t)(e - b);
@@ -847,6 +953,11 @@ gicp_status seg_static_cloud_dev(ddlo_seg* o, const int32_t* remove_ids, size_t 
   HIP_TRY(o->vscratch.ensure(sizeof(int) * voxel_scratch_ints(n)));
   HIP_TRY(o->cubtmp.ensure(std::max(crop_box_tmp_bytes(n), voxel_tmp_bytes(n))));
   launch_pack4(o->s, o->raw.as<unsigned char>(), o->raw_stride, n, o->f4.as<float4>());
+  if (dev_label && n_remove) {
+    HIP_TRY(rt::grow(o->dids, sizeof(int) * n_remove, o->s));
+    HIP_TRY(hipMemcpyAsync(o->dids.p, drop, sizeof(int) * n_remove, hipMemcpyHostToDevice, o->s));
+    if (gicp_status st = label_device_drop(o->s, o->ldev, o->dids.as<int>(), (int)n_remove, o->f4.as<float4>())) return st;
+  }
   if (ndrop) {
     HIP_TRY(hipMemcpyAsync(o->ddrop.p, drop, sizeof(int) * ndrop, hipMemcpyHostToDevice, o->s));
     k_static_drop<<<cdiv_s((long)ndrop, 256), 256, 0, o->s>>>(o->ddrop.as<int>(), (int)ndrop, o->f4.as<float4>());
@@ -940,6 +1051,43 @@ gicp_status ddlo_seg_static_cloud(ddlo_seg* o, const int32_t* remove_ids, size_t
     out[3 * i + 1] = h[i].y;
     out[3 * i + 2] = h[i].z;
   }
+  return GICP_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
+
+gicp_status ddlo_seg_set_labelling(ddlo_seg* o, int mode) {
+  if (!o) return fail(GICP_EINVAL, "null handle");
+  if (mode != DDLO_SEG_LABEL_HOST && mode != DDLO_SEG_LABEL_DEVICE) return fail(GICP_EINVAL, "unknown labelling mode");
+  if (mode == DDLO_SEG_LABEL_DEVICE) {
+    if (!label_device_window_ok(o->p))
+      return fail(GICP_EINVAL, "device labelling needs 0 <= win_col0 and win_col1 <= cols - 1");
+    if (!o->rec_pin) {
+      HIP_TRY(hipSetDevice(o->device));
+      HIP_TRY(hipHostMalloc((void**)&o->rec_pin, kRecPinBytes, hipHostMallocDefault));
+    }
+  }
+  if (mode != o->labelling) {   // the last scan's results belong to the other mode's data
+    o->have = false;
+    o->have_objects = false;
+  }
+  o->labelling = mode;
+  return GICP_OK;
+}
+
+gicp_status ddlo_seg_get_labelling(const ddlo_seg* o, int* mode) {
+  if (!o || !mode) return fail(GICP_EINVAL, "null argument");
+  *mode = o->labelling;
+  return GICP_OK;
+}
+
+gicp_status ddlo_seg_labelling_stats(const ddlo_seg* o, int32_t* replayed, int32_t* longest_prefix) {
+  if (!o) return fail(GICP_EINVAL, "null handle");
+  if (!o->have || o->labelling != DDLO_SEG_LABEL_DEVICE) return fail(GICP_EINVAL, "no scan processed in device mode");
+  if (replayed) *replayed = o->replayed;
+  if (longest_prefix) *longest_prefix = o->longest_prefix;
   return GICP_OK;
 }
 

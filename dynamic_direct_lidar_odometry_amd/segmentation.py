@@ -4,7 +4,10 @@
 (``src/detection/detection.cpp``) that OdomNode::applySegmentation drives
 (``odom.cc:853-857``): projectScan, projectResiduals, groundRemoval and
 cloudSegmentation / labelComponents on one organized scan.  The per-pixel
-passes run on the GPU, the order-dependent labelling on the host.
+passes run on the GPU; the labelling on the host (the default: the reference's
+breadth-first search, literally) or on the GPU (``labelling="device"``: the
+same labels and segment count, average residuals summed in double in row-major
+order).
 """
 from __future__ import annotations
 
@@ -15,9 +18,10 @@ import numpy as np
 from . import GicpError, _ptr, load
 
 __all__ = ["SegParams", "SegResult", "SegObject", "OBJECT_DTYPE", "Segmentation", "default_seg_params",
-           "yaml_seg_params", "label_components", "objects_from", "EXCLUDED", "UNLABELLED", "REJECTED"]
+           "yaml_seg_params", "label_components", "label_components_device", "objects_from", "LABELLING", "EXCLUDED", "UNLABELLED", "REJECTED"]
 
 EXCLUDED, UNLABELLED, REJECTED = -1, 0, 999999
+LABELLING = {"host": 0, "device": 1}   # DDLO_SEG_LABEL_*
 
 
 class SegParams(C.Structure):
@@ -95,6 +99,10 @@ def _lib():
             "ddlo_seg_ground_indices": (I, [P, P, S, C.POINTER(S)]),
             "ddlo_seg_label_indices": (I, [P, P, S, P, S, C.POINTER(S)]),
             "ddlo_seg_label": (I, [C.POINTER(SegParams), P, P, P, F, P, P, S, C.POINTER(C.c_int32)]),
+            "ddlo_seg_label_device": (I, [I, C.POINTER(SegParams), P, P, P, F, P, P, S, C.POINTER(C.c_int32)]),
+            "ddlo_seg_set_labelling": (I, [P, I]),
+            "ddlo_seg_get_labelling": (I, [P, C.POINTER(I)]),
+            "ddlo_seg_labelling_stats": (I, [P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
             "ddlo_seg_objects": (I, [P, F, P, S, C.POINTER(S)]),
             "ddlo_seg_objects_from": (I, [I, P, S, I, I, P, P, S, F, P, S, C.POINTER(S)]),
             "ddlo_seg_static_cloud": (I, [P, P, S, P, C.c_double, C.c_double, P, S, C.POINTER(S)]),
@@ -129,9 +137,10 @@ def yaml_seg_params(**kw) -> SegParams:
     return p.replace(**kw) if kw else p
 
 
-def label_components(p: SegParams, range_img, z_img, label_img, sensor_z: float, residual=None):
+def label_components(p: SegParams, range_img, z_img, label_img, sensor_z: float, residual=None, device=None):
     """The host labelling alone (ddlo_seg_label) over caller images; returns
-    (label image, avg residuals by label, segments)."""
+    (label image, avg residuals by label, segments).  device: the GPU to label on
+    instead (ddlo_seg_label_device, see label_components_device)."""
     rng = np.ascontiguousarray(range_img, np.float32).reshape(-1)
     z = np.ascontiguousarray(z_img, np.float32).reshape(-1)
     lab = np.ascontiguousarray(label_img, np.int32).reshape(-1).copy()
@@ -143,9 +152,21 @@ def label_components(p: SegParams, range_img, z_img, label_img, sensor_z: float,
         raise ValueError("residual image must have rows x cols pixels")
     avg = np.zeros(n + 1, np.float64)
     seg = C.c_int32()
-    _check(_lib().ddlo_seg_label(C.byref(p), _ptr(rng), _ptr(z), None if res is None else _ptr(res), float(sensor_z),
-                                 _ptr(lab), _ptr(avg), avg.size, C.byref(seg)))
+    args = (C.byref(p), _ptr(rng), _ptr(z), None if res is None else _ptr(res), float(sensor_z), _ptr(lab), _ptr(avg),
+            avg.size, C.byref(seg))
+    if device is None:
+        _check(_lib().ddlo_seg_label(*args))
+    else:
+        _check(_lib().ddlo_seg_label_device(int(device), *args))
     return lab.reshape(p.rows, p.cols), avg[: seg.value + 1], seg.value
+
+
+def label_components_device(p: SegParams, range_img, z_img, label_img, sensor_z: float, residual=None, device: int = 0):
+    """label_components on the GPU (ddlo_seg_label_device): the same labels and segment
+    count; the average residuals are the positive residuals of a segment's pixels without
+    its seed, summed in double in row-major order, over their count.  The window must lie
+    inside the columns."""
+    return label_components(p, range_img, z_img, label_img, sensor_z, residual, device=device)
 
 
 def objects_from(xyz_t, label, avg_residual=None, max_dim_ratio: float = 10.0, device: int = 0) -> np.ndarray:
@@ -173,12 +194,34 @@ def objects_from(xyz_t, label, avg_residual=None, max_dim_ratio: float = 10.0, d
 class Segmentation:
     """DetectionModule's segmentation on device ``device`` (ddlo_seg_*)."""
 
-    def __init__(self, device: int = 0, params: SegParams | None = None):
+    def __init__(self, device: int = 0, params: SegParams | None = None, labelling: str = "host"):
         self.L = _lib()
         self.params = params if params is not None else default_seg_params()
         self.h = C.c_void_p()
         _check(self.L.ddlo_seg_create(device, C.byref(self.params), C.byref(self.h)))
         self.last: SegResult | None = None
+        if labelling != "host":
+            self.labelling = labelling
+
+    @property
+    def labelling(self) -> str:
+        """"host" or "device" (ddlo_seg_set_labelling); setting "device" on a handle whose window
+        reaches outside the columns raises GicpError and leaves the mode unchanged."""
+        m = C.c_int()
+        _check(self.L.ddlo_seg_get_labelling(self.h, C.byref(m)))
+        return {v: k for k, v in LABELLING.items()}[m.value]
+
+    @labelling.setter
+    def labelling(self, mode: str):
+        if mode not in LABELLING:
+            raise ValueError('labelling must be "host" or "device"')
+        _check(self.L.ddlo_seg_set_labelling(self.h, LABELLING[mode]))
+
+    def labelling_stats(self):
+        """Device mode: (components whose push prefix was replayed, longest prefix) of the last scan."""
+        a, b = C.c_int32(), C.c_int32()
+        _check(self.L.ddlo_seg_labelling_stats(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def close(self):
         if self.h:

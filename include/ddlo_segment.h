@@ -1,8 +1,8 @@
 /*
  * ddlo_segment.h — C-ABI of the range-image segmentation that feeds DDLO's
- * dynamic-object detection (host-side per the north
- * star; the per-pixel passes run on the device, the order-dependent labelling
- * on the host).
+ * dynamic-object detection (the per-pixel passes run
+ * on the device; the labelling on the host by default, or on the device:
+ * ddlo_seg_set_labelling).
  *
  * Replaces DetectionModule (reference
  * dynamic_direct_lidar_odometry/src/detection/detection.cpp,
@@ -17,7 +17,8 @@
  *                      labelComponents :544-724
  *   ddlo_seg_ground_indices   getGroundIndices :1002-1013
  *   ddlo_seg_label_indices    label_indices_i_ (cloudSegmentation :524-538)
- *   ddlo_seg_label     labelComponents over caller-provided images (host only)
+ *   ddlo_seg_label / ddlo_seg_label_device
+ *                      labelComponents over caller-provided images
  *   ddlo_seg_objects / ddlo_seg_objects_from
  *                      computeAllObjects / getObject :726-818: one oriented
  *                      bounding box per segment, on the device (one workgroup
@@ -137,5 +138,7 @@ gicp_status ddlo_seg_label(const ddlo_seg_params* p, const float* range, const f
 
 /* ddlo_seg_object, ddlo_seg_objects, ddlo_seg_objects_from, ddlo_seg_static_cloud */
 #include "ddlo_seg_objects.h"
+/* ddlo_seg_set_labelling, ddlo_seg_get_labelling, ddlo_seg_label_device, ddlo_seg_labelling_stats */
+#include "ddlo_seg_label.h"
 
 #endif /* DDLO_SEGMENT_H */
