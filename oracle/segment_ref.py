@@ -36,6 +36,11 @@ def atan2f(y, x) -> np.float32:
     return F32(_libm.atan2f(float(y), float(x)))
 
 
+def atan2_rd(y, x) -> np.float32:
+    """atan2f as the float rounding of the double atan2 (the device's definition, csrc/segment.hip)."""
+    return F32(np.arctan2(np.float64(y), np.float64(x)))
+
+
 def project_scan(xyz_t: np.ndarray, T: np.ndarray, rows: int, cols: int, minimum_range: float):
     """projectScan (:292-329): range_mat_ and full_cloud_ (NaN where no range)."""
     p = np.asarray(xyz_t, np.float32)[:, :3].reshape(rows * cols, 3)
@@ -53,9 +58,10 @@ def project_scan(xyz_t: np.ndarray, T: np.ndarray, rows: int, cols: int, minimum
     return rng.reshape(rows, cols), full.reshape(rows, cols, 3)
 
 
-def ground_removal(full: np.ndarray, rng: np.ndarray, ground_rows: int, mount: float, thr: float):
+def ground_removal(full: np.ndarray, rng: np.ndarray, ground_rows: int, mount: float, thr: float, atan2=atan2f):
     """groundRemoval (:458-504): ground_mat_ (int8) and the -1 / 0 label_mat_.
-    Vectorised over columns; rows in the reference's bottom-up order."""
+    Vectorised over columns; rows in the reference's bottom-up order.
+    atan2: the float atan2 of the angle (libm's atan2f, or atan2_rd)."""
     H, W = rng.shape
     ground = np.zeros((H, W), np.int8)
     for ri in range(ground_rows):
@@ -65,7 +71,7 @@ def ground_removal(full: np.ndarray, rng: np.ndarray, ground_rows: int, mount: f
         with np.errstate(invalid="ignore"):
             d = up - lo
             s = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1])
-            a = np.array([atan2f(dz, sv) for dz, sv in zip(d[:, 2], s)], np.float32)
+            a = np.array([atan2(dz, sv) for dz, sv in zip(d[:, 2], s)], np.float32)
             angle = ((a * F32(180)).astype(np.float64) / np.pi).astype(np.float32)
             g = np.abs(angle - F32(mount)) <= F32(thr)
         ground[row, noinfo] = -1
@@ -174,12 +180,13 @@ def label_components(p, rng: np.ndarray, z: np.ndarray, label: np.ndarray, senso
     return label.astype(np.int32), np.array(avg), label_count - 1
 
 
-def segment(p, xyz_t: np.ndarray, T: np.ndarray, residual=None):
+def segment(p, xyz_t: np.ndarray, T: np.ndarray, residual=None, atan2=atan2f):
     """The whole DetectionModule pass ddlo_seg_process replaces: returns
-    (range, ground, label, avg_residuals, segments)."""
+    (range, ground, label, avg_residuals, segments).  atan2: groundRemoval's
+    (see ground_removal); the labelling keeps libm's."""
     T = np.asarray(T, np.float32).reshape(4, 4)
     rng, full = project_scan(xyz_t, T, p.rows, p.cols, p.minimum_range)
-    ground, label = ground_removal(full, rng, p.ground_rows, p.sensor_mount_angle, p.ground_angle_threshold)
+    ground, label = ground_removal(full, rng, p.ground_rows, p.sensor_mount_angle, p.ground_angle_threshold, atan2)
     z = np.asarray(xyz_t, np.float32)[:, 2].reshape(p.rows, p.cols)
     label, avg, nseg = label_components(p, rng, z, label, float(T[2, 3]), residual)
     return rng, ground, label, avg, nseg

@@ -9,9 +9,19 @@ detection.cpp:203-252).
 (2) End to end: against the restatement applied to the CPU oracle's residuals
     of the same align (sqrt of sq_distances_), |d| <= 1e-5 m on pixels the two
     assign to the same point.
+(3) The rule that makes the kernels non-trivial, on a 32 x 512 scan with hand-built
+    points before and after it, in five geometries: the highest original index
+    on a pixel wins (thousands of collisions in the coarse images), and
+    static_cast<int> truncates toward zero, so a quotient in (-1, 0) lands in
+    row / column 0.  Every pixel is bit-exact in img and xyz except those that
+    an undecided point can reach: a point whose bucket changes when theta or phi
+    moves by 4 double ulps (device and host atan2 may differ there), at most
+    1e-3 of the kept points.
 The reference's atan2/sqrt overloads on float members depend on the headers
 reaching odom.cc (float vs double); parity of those boundary pixels is
 unpinned."""
+import math
+
 import numpy as np
 import pytest
 
@@ -70,3 +80,170 @@ def test_image_geometry_and_state_errors(aligned):
     fresh = P.Context(0)
     with pytest.raises(P.GicpError):
         fresh.residual_image()
+
+
+# ---- (3) collisions, truncation, hand-built points ------------------------------------------------
+P3 = (0.75, 0.25, 3.0)                      # the same point at four indices: the last one wins
+HAND = [P3,
+        (0.0, 0.5, 4.0),                    # x = 0, z > 0: theta 0
+        (0.0, 0.5, -4.0),                   # x = +0, z < 0: theta pi
+        (-0.0, 0.5, -4.0),                  # x = -0, z < 0: theta -pi
+        (1.0, 0.0, 2.0),                    # y = +0: phi 0
+        (1.0, -0.0, 2.0),                   # y = -0: phi -0
+        (0.0, 1.0, 0.0),                    # x = z = 0: theta 0 (phi pi / 2)
+        (-1e-30, 0.3, 1.0)]                 # theta = -1e-30
+# 200 points on the ray through (3, 1, 4), 0.64 m to 72 m, each scale exact in float; the
+# ranges jump about by index, so the points are spread over the Morton order
+RAY = [tuple((256 + j) * 2.0 ** (j % 7 - 11) * c for c in (3.0, 1.0, 4.0)) for j in range(200)]
+BLOCK = np.array(HAND + RAY + [P3], np.float32)
+NH = len(HAND)
+
+# (theta_min, theta_max, W, H), then the expected (u, v) of HAND[0..7] and of the ray (None: skipped)
+GEOMETRIES = {
+    "default": ((-math.pi / 3, math.pi / 3, 512, 512),
+                [(315, 275), (256, 286), None, None, (369, 256), (369, 256), None, (256, 327)], (413, 304)),
+    "coarse_quadrant": ((0.0, math.pi / 2, 37, 5),
+                        [(5, 0), (0, 0), None, None, (10, 0), (10, 0), None, (0, 0)], (15, 0)),      # -1e-30: column 0
+    "full_circle": ((-math.pi, math.pi, 64, 32),
+                    [(34, 16), (32, 16), None, (0, 16), (36, 16), (36, 16), (32, 24), (32, 17)], (38, 17)),  # pi: u == W
+    "one_pixel": ((-math.pi / 3, math.pi / 3, 1, 1),
+                  [(0, 0), (0, 0), None, None, (0, 0), (0, 0), None, (0, 0)], (0, 0)),
+    "narrow_wide": ((-0.2, 0.2, 300, 3), [None, (150, 2), None, None, None, None, None, None], None),
+}
+
+
+def quotients(points, tmin, tmax, W, H, dtheta=0, dphi=0):
+    """The float64 quotients (qu, qv) whose truncation is a point's pixel, in the restatement's
+    arithmetic; dtheta / dphi move an angle by that many double ulps where both arguments of
+    its atan2 are non-zero (with a zero argument the result is exact)."""
+    p = np.asarray(points, np.float32).reshape(-1, 3)
+    x, y, z = (p[:, k].astype(np.float64) for k in range(3))
+    r = np.sqrt((p[:, 0] * p[:, 0] + p[:, 2] * p[:, 2]).astype(np.float64))
+    theta, phi = np.arctan2(x, z), np.arctan2(y, r)
+    theta = np.where((x != 0) & (z != 0), theta + dtheta * np.spacing(theta), theta)
+    phi = np.where((y != 0) & (r != 0), phi + dphi * np.spacing(phi), phi)
+    return (theta - tmin) / (tmax - tmin) * W, (phi - tmin) / (tmax - tmin) * H
+
+
+def buckets(points, geom, dtheta=0, dphi=0):
+    """(u, v, kept) per point."""
+    tmin, tmax, W, H = geom
+    qu, qv = quotients(points, tmin, tmax, W, H, dtheta, dphi)
+    u, v = qu.astype(np.int64), qv.astype(np.int64)      # static_cast<int>: toward zero
+    return u, v, (u >= 0) & (u < W) & (v >= 0) & (v < H)
+
+
+def analyse(src, geom):
+    """What the restatement alone says about a cloud in one geometry: buckets, collisions, points kept
+    only through truncation toward zero, the undecided points, and the pixels whose winner one of
+    them could change (it can reach the pixel and outranks the decided points' winner there)."""
+    tmin, tmax, W, H = geom
+    n = len(src)
+    u, v, kept = buckets(src, geom)
+    qu, qv = quotients(src, *geom)
+    moved = [buckets(src, geom, dt, dp) for dt in (-4, 0, 4) for dp in (-4, 0, 4)]
+    undecided = np.zeros(n, bool)
+    for u2, v2, k2 in moved:
+        undecided |= (k2 != kept) | (kept & k2 & ((u2 != u) | (v2 != v)))
+    decided = np.full(W * H, -1, np.int64)
+    m = kept & ~undecided
+    np.maximum.at(decided, (v * W + u)[m], np.flatnonzero(m))
+    excluded = np.zeros(W * H, bool)
+    for u2, v2, k2 in moved:
+        m = undecided & k2
+        pix = (v2 * W + u2)[m]
+        excluded[pix[np.flatnonzero(m) > decided[pix]]] = True
+    return dict(u=u, v=v, kept=kept, undecided=undecided, excluded=excluded.reshape(H, W),
+                collisions=int(kept.sum()) - len(set((v * W + u)[kept].tolist())),
+                truncated=int((kept & (((qu > -1) & (qu < 0)) | ((qv > -1) & (qv < 0)))).sum()))
+
+
+@pytest.fixture(scope="module")
+def edge_cloud():
+    scan, tgt, _ = scene.s2s_pair(32, 512, 1)
+    src = np.concatenate([BLOCK, scan, BLOCK])
+    return src, tgt, {name: analyse(src, g[0]) for name, g in GEOMETRIES.items()}
+
+
+@pytest.fixture(scope="module")
+def edge_aligned(edge_cloud):
+    src, tgt, _ = edge_cloud
+    c = P.Context(0)
+    c.set_params(P.default_params(**S2S))
+    c.set_target(tgt)
+    c.set_source(src)
+    c.align()
+    return c, src, c.residuals()
+
+
+def test_undecided_points_are_rare(edge_cloud):
+    """At most 1e-3 of the kept points, over the five geometries together: 28 of 28,556.  They are the
+    scan's column at azimuth 270 degrees, whose x = r cos(270 deg) is about -7e-16, so theta is one
+    double ulp from -pi (z < 0) or from 0.  With theta_min = -pi that is a quotient at 0, with
+    theta_min = -pi / 3 a quotient one ulp above -1, where the truncation toward zero stops keeping
+    a point: 15 of 16,787 kept points in the full circle, 13 of 7,998 in the one-pixel image (1.6e-3
+    of that image's points alone), none in the other three.  An undecided point matters only where
+    it outranks the decided points' winner: 2 pixels of the full circle, none elsewhere."""
+    _, _, info = edge_cloud
+    undecided = sum(int(a["undecided"].sum()) for a in info.values())
+    kept = sum(int(a["kept"].sum()) for a in info.values())
+    for name, a in info.items():
+        print(name, int(a["undecided"].sum()), "undecided of", int(a["kept"].sum()), "kept;",
+              int(a["excluded"].sum()), "pixels excluded")
+    assert undecided <= 1e-3 * kept, f"{undecided} undecided of {kept} kept points"
+    assert sum(int(a["excluded"].sum()) for a in info.values()) <= 2
+
+
+@pytest.mark.parametrize("name", sorted(GEOMETRIES))
+def test_collisions_truncation_and_hand_points(edge_cloud, edge_aligned, name):
+    c, src, res = edge_aligned
+    a = edge_cloud[2][name]
+    geom, hand_px, ray_px = GEOMETRIES[name]
+    tmin, tmax, W, H = geom
+    n = len(src)
+    second = n - len(BLOCK)                  # the second block's first index
+    # ---- what the reference alone says about this input
+    u, v, kept, reach = a["u"], a["v"], a["kept"], a["excluded"]
+    for k, want in enumerate(hand_px):
+        for at in (k, second + k):
+            assert ((int(u[at]), int(v[at])) if kept[at] else None) == want, (k, at)
+    ray = np.arange(second + NH, second + NH + len(RAY))
+    assert all(((int(u[i]), int(v[i])) if kept[i] else None) == ray_px for i in ray)
+    if name in ("coarse_quadrant", "full_circle"):
+        assert a["collisions"] > 1000
+    if name == "coarse_quadrant":
+        assert a["truncated"] > 100
+    # ---- the device
+    img, xyz = c.residual_image(tmin, tmax, W, H, with_xyz=True)
+    assert img.shape == (H, W) and xyz.shape == (H, W, 3)
+    oimg, owin = O.residual_image(src, res, tmin, tmax, W, H)
+    oxyz = np.where((owin >= 0)[..., None], src[np.maximum(owin, 0)], np.float32(0))
+    sure = ~reach
+    assert np.array_equal(img.view(np.uint32)[sure], oimg.view(np.uint32)[sure])
+    assert np.array_equal(xyz.view(np.uint32)[sure], oxyz.view(np.uint32)[sure])     # the winner's source point
+    empty = sure & (owin < 0)
+    assert not img[empty].any() and not xyz[empty].any()
+    assert empty.any() or name in ("one_pixel", "coarse_quadrant", "full_circle")
+    # ---- the hand-built points, literally
+    def winner_is(px, index):
+        uu, vv = px
+        assert not reach[vv, uu]
+        assert xyz[vv, uu].tobytes() == src[index].tobytes() and img[vv, uu] == np.float32(res[index])
+
+    if hand_px[0] is not None:               # P3 at indices 0 < NH + 200 < second < n - 1: the last wins
+        assert all(src[i].tobytes() == src[n - 1].tobytes() for i in (0, NH + len(RAY), second))
+        winner_is(hand_px[0], n - 1)
+    if ray_px is not None and ray_px != hand_px[0]:
+        rr = np.linalg.norm(src[ray].astype(np.float64), axis=1)
+        assert rr.min() < rr[-1] < rr.max()  # the highest index is neither the nearest nor the farthest
+        winner_is(ray_px, int(ray[-1]))
+    if name == "coarse_quadrant":            # theta = -1e-30 truncates into column 0 and outranks HAND[1] there
+        winner_is((0, 0), second + 7)
+    if name == "full_circle":
+        winner_is((0, 16), second + 3)       # theta = -pi: column 0; theta = +pi is u == W, skipped
+        winner_is((32, 24), second + 6)      # x = z = 0
+    if name in ("default", "full_circle"):
+        winner_is(hand_px[5], second + 5)    # y = -0 after y = +0 on the same pixel: xyz keeps the sign
+        winner_is(hand_px[1], second + 1)
+    if name == "narrow_wide":
+        winner_is((150, 2), second + 1)
