@@ -10,7 +10,7 @@ LIBDIR := $(PKG)/_lib
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function
 # the hot path, one file per stage (K1 .. K6), then the other translation units
 STAGES := index_build covariance corr_search moments outputs
-SRCS := $(STAGES) knn_tasks nftree cellgrid tietree capi preprocess odom segment seg_label map
+SRCS := $(STAGES) knn_tasks nftree cellgrid tietree capi preprocess odom segment seg_label seg_tracks map track
 OBJS := $(SRCS:%=$(LIBDIR)/%.o)
 
 all: lib oracle facade raycast

@@ -46,12 +46,14 @@
 
 #include "../../include/ddlo_gicp.h"
 #include "../../include/ddlo_odom.h"
+#include "../../include/ddlo_track.h"
 #include "gicp_types.hpp"
 #include "launch.hpp"
 #include "runtime.hpp"
 #include "devknobs.hpp"
 #include "seg_internal.hpp"
 #include "odom_internal.hpp"
+#include "track_internal.hpp"
 
 namespace {
 
@@ -500,6 +502,11 @@ struct ddlo_odom {
   std::vector<ddlo_seg_object> dyn_objs;
   std::vector<uint8_t> dyn_flags;
   std::vector<int32_t> dyn_remove;
+  // process_tracked: time_prev_ (detection.cpp:62,824-825: it starts at 0 and advances only
+  // on the frames that run the segmentation), and the frame's scratch
+  double time_prev = 0.0;
+  std::vector<int32_t> trk_ids, trk_set, trk_seg, trk_dead, trk_live, trk_status;
+  std::vector<ddlo_map_box> trk_boxes;
 };
 
 // the dynamic-object step's arguments (ddlo_odom_process_dynamic)
@@ -509,6 +516,12 @@ struct DynStep {
   ddlo_nonstatic_fn decide;
   void* user;
   ddlo_seg_result* seg_res;
+  // ddlo_odom_process_tracked: the tracker decides, and the lists of its
+  // non-static tracks (stale ones included) are what the keyframe loses
+  ddlo_track* track = nullptr;
+  ddlo_map* map = nullptr;
+  double stamp = 0.0;
+  ddlo_track_result* track_res = nullptr;
 };
 
 namespace {
@@ -642,15 +655,80 @@ gicp_status make_keyframe(ddlo_odom* o, const std::shared_ptr<CloudData>& scan) 
 gicp_status make_keyframe_static(ddlo_odom* o, const DynStep& d) {
   const float4* pts = nullptr;
   int n = 0;
-  gicp_status st = seg_static_cloud_dev(d.seg, o->dyn_remove.data(), o->dyn_remove.size(), o->pose,
-                                        o->p.crop_use ? o->p.crop_size : 0.0, o->p.vf_scan_use ? o->p.vf_scan_res : 0.0,
-                                        &pts, &n);
+  const double crop = o->p.crop_use ? o->p.crop_size : 0.0, leaf = o->p.vf_scan_use ? o->p.vf_scan_res : 0.0;
+  gicp_status st = d.track ? seg_static_cloud_tracks_dev(d.seg, o->dyn_remove.data(), o->dyn_remove.size(), o->pose, crop,
+                                                         leaf, &pts, &n, nullptr)
+                           : seg_static_cloud_dev(d.seg, o->dyn_remove.data(), o->dyn_remove.size(), o->pose, crop, leaf,
+                                                  &pts, &n);
   if (st) return st;
   if (n < 1) return fail(GICP_ETOOFEW, "keyframe without points");
   // (o->a is free: metrics() has waited for the median kernel, its last reader)
   HIP_TRY(o->a.ensure(sizeof(float4) * (size_t)n));
   HIP_TRY(hipMemcpyAsync(o->a.p, pts, sizeof(float4) * (size_t)n, hipMemcpyDeviceToDevice, o->s));
   return make_keyframe_from_a(o, n);
+}
+
+// trackDetections (detection.cpp:820-832) and what applySegmentation takes
+// from the tracker (odom.cc:867-892), after the frame's objects: dt = stamp -
+// time_prev_, TrackingModule::update, the pixel lists of the tracks this
+// frame's detections updated or created replaced by their segments' and the
+// erased tracks' released (ddlo_seg_tracks_sync), then dyn_remove = the ids
+// of every UNDEFINED or DYNAMIC track: their lists, the stale ones of
+// coasting tracks included, are what the keyframe loses.  With a map, the
+// box histories of the tracks that turned dynamic are cleared from it.
+// The tracker and time_prev_ advance first, as in the reference; an error in
+// a later step (the sync, the map, the keyframe) leaves the tracker one frame
+// ahead of the lists, and as every error of this driver it leaves the driver
+// unusable (ddlo_odom.h): destroy the three handles together.  The collected
+// boxes are taken from the tracker only once the sync has succeeded.
+gicp_status tracked_step(ddlo_odom* o, const DynStep& d) {
+  const size_t k = o->dyn_objs.size();
+  const double dt = d.stamp - o->time_prev;
+  o->time_prev = d.stamp;
+  o->trk_ids.assign(k + 1, -1);
+  ddlo_track_result tr{};
+  gicp_status st = ddlo_track_update(d.track, dt, o->dyn_objs.data(), k, o->trk_ids.data(), &tr);
+  if (st) return st;
+  track_live(d.track, o->trk_live, o->trk_status);
+  const std::vector<int>& erased = track_erased(d.track);
+  // a track created and erased within this update (max_no_hits 0) never held a list
+  o->trk_set.clear();
+  o->trk_seg.clear();
+  for (size_t i = 0; i < k; ++i)
+    if (std::find(o->trk_live.begin(), o->trk_live.end(), o->trk_ids[i]) != o->trk_live.end()) {
+      o->trk_set.push_back(o->trk_ids[i]);
+      o->trk_seg.push_back(o->dyn_objs[i].id);
+    }
+  o->trk_dead.clear();
+  for (int id : erased)
+    if (std::find(o->trk_ids.begin(), o->trk_ids.begin() + (long)k, id) == o->trk_ids.begin() + (long)k)
+      o->trk_dead.push_back(id);
+  st = ddlo_seg_tracks_sync(d.seg, o->trk_set.data(), o->trk_seg.data(), o->trk_set.size(), o->trk_dead.data(),
+                            o->trk_dead.size());
+  if (st) return st;
+  o->dyn_remove.clear();
+  for (size_t i = 0; i < o->trk_live.size(); ++i)
+    if (o->trk_status[i] != DDLO_TRACK_STATIC) o->dyn_remove.push_back(o->trk_live[i]);
+  for (int32_t id : o->dyn_remove) {
+    size_t len = 0;
+    st = ddlo_seg_track_indices(d.seg, id, nullptr, 0, &len);
+    if (st) return st;
+    tr.indices_dropped += (int64_t)len;
+  }
+  size_t nb = 0;
+  st = ddlo_track_take_cleared_boxes(d.track, nullptr, 0, &nb);
+  if (st) return st;
+  o->trk_boxes.resize(nb);
+  if (nb) {
+    st = ddlo_track_take_cleared_boxes(d.track, o->trk_boxes.data(), nb, &nb);
+    if (st) return st;
+    if (d.map) {
+      st = ddlo_map_clear_boxes(d.map, o->trk_boxes.data(), nb, nullptr);
+      if (st) return st;
+    }
+  }
+  if (d.track_res) *d.track_res = tr;
+  return GICP_OK;
 }
 
 // OdomNode::applySegmentation up to the tracker's verdict (odom.cc:853-870),
@@ -684,6 +762,7 @@ gicp_status dynamic_step(ddlo_odom* o, const DynStep& d, int npix, size_t stride
   st = seg_objects_vec(d.seg, d.dp.max_dim_ratio, o->dyn_objs);
   if (st) return st;
   const size_t k = o->dyn_objs.size();
+  if (d.track) return tracked_step(o, d);
   o->dyn_flags.assign(k + 1, 0);
   if (d.decide) {
     if (d.decide(d.user, o->dyn_objs.data(), k, o->dyn_flags.data()) != 0)
@@ -990,6 +1069,10 @@ static gicp_status process_scan(ddlo_odom* o, const float* xyz, size_t n, size_t
     if (st) return st;
     metrics();
     o->have_target = true;
+    if (dyn && dyn->map) {   // MapNode::keyframeCB receives the first keyframe as every other
+      st = ddlo_map_add_odom_keyframe(dyn->map, o, (int)o->keyframes.size() - 1, nullptr);
+      if (st) return st;
+    }
     res->status = DDLO_ODOM_FIRST;
     res->keyframe_added = 1;
     res->num_keyframes = (int)o->keyframes.size();
@@ -1060,6 +1143,10 @@ static gicp_status process_scan(ddlo_odom* o, const float* xyz, size_t n, size_t
       st = dyn ? make_keyframe_static(o, *dyn) : make_keyframe(o, scan);
       if (st) return st;
       res->keyframe_added = 1;
+      if (dyn && dyn->map) {   // MapNode::keyframeCB for the keyframe just published
+        st = ddlo_map_add_odom_keyframe(dyn->map, o, (int)o->keyframes.size() - 1, nullptr);
+        if (st) return st;
+      }
     }
   }
   mark(6);
@@ -1102,6 +1189,28 @@ gicp_status ddlo_odom_process_dynamic(ddlo_odom* o, ddlo_seg* seg, const float* 
   else ddlo_dynamic_default_params(&d.dp);
   if (!(d.dp.theta_max > d.dp.theta_min)) return fail(GICP_EINVAL, "theta_max must exceed theta_min");
   if (seg_res) std::memset(seg_res, 0, sizeof(*seg_res));
+  return process_scan(o, xyz, (size_t)sp.rows * sp.cols, stride, res, &d);
+}
+
+gicp_status ddlo_odom_process_tracked(ddlo_odom* o, ddlo_seg* seg, ddlo_track* track, ddlo_map* map, const float* xyz,
+                                      size_t stride, double stamp, const ddlo_dynamic_params* dp, ddlo_odom_result* res,
+                                      ddlo_seg_result* seg_res, ddlo_track_result* track_res) {
+  if (!o || !seg || !track || !xyz || !res) return fail(GICP_EINVAL, "null argument");
+  if (seg_device(seg) != o->device) return fail(GICP_EINVAL, "the segmentation lives on another device");
+  if (!std::isfinite(stamp)) return fail(GICP_EINVAL, "non-finite stamp");
+  ddlo_seg_params sp;
+  gicp_status st = seg_get_params(seg, &sp);
+  if (st) return st;
+  DynStep d{seg, {}, nullptr, nullptr, seg_res};
+  d.track = track;
+  d.map = map;
+  d.stamp = stamp;
+  d.track_res = track_res;
+  if (dp) d.dp = *dp;
+  else ddlo_dynamic_default_params(&d.dp);
+  if (!(d.dp.theta_max > d.dp.theta_min)) return fail(GICP_EINVAL, "theta_max must exceed theta_min");
+  if (seg_res) std::memset(seg_res, 0, sizeof(*seg_res));
+  if (track_res) std::memset(track_res, 0, sizeof(*track_res));
   return process_scan(o, xyz, (size_t)sp.rows * sp.cols, stride, res, &d);
 }
 

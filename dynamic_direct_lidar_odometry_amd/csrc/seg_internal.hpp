@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <vector>
 
 #include "../../include/ddlo_segment.h"
@@ -21,6 +22,36 @@ gicp_status seg_objects_vec(ddlo_seg* s, float max_dim_ratio, std::vector<ddlo_s
 // until the next call on s) and *count; complete when the call returns.
 gicp_status seg_static_cloud_dev(ddlo_seg* s, const int32_t* remove_ids, size_t n_remove, const float centre[3],
                                  double crop_size, double leaf, const float4** pts, int* count);
+// the same with one more removal between the packing and the crop / voxel
+// pass: more(stream, packed scan, pixels) may write NaN over further points
+using SegDropHook = std::function<gicp_status(hipStream_t, float4*, int)>;
+gicp_status seg_static_cloud_with(ddlo_seg* s, const int32_t* remove_ids, size_t n_remove, const float centre[3],
+                                  double crop_size, double leaf, const float4** pts, int* count, const SegDropHook* more);
+
+// The tracks' pixel lists (seg_tracks.hip) live in the segmentation handle;
+// what they need of it: its stream and image size, and the last scan's
+// segments as CSR on the device (device labelling: the labelling's own; host
+// labelling: the upload made for k_seg_objects, made here if the objects were
+// not asked for) with every segment's length on the host.
+struct SegTracks;
+void seg_tracks_free(SegTracks* t);
+struct SegTrackView {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  int npix = 0;
+  bool have = false;           // a scan was processed
+  int segments = 0;
+  // with_csr only:
+  const int* d_off = nullptr;  // segments + 2 offsets
+  const int* d_pix = nullptr;
+  std::vector<int> len;        // [l] for l = 1 .. segments
+  SegTracks** slot = nullptr;
+};
+gicp_status seg_tracks_view(ddlo_seg* s, SegTrackView* v, bool with_csr);
+// ddlo_seg_static_cloud_tracks, the result left on the device as seg_static_cloud_dev
+// leaves it; *dropped (optional) = the sum of the removed lists' lengths
+gicp_status seg_static_cloud_tracks_dev(ddlo_seg* s, const int32_t* track_ids, size_t n, const float centre[3],
+                                        double crop_size, double leaf, const float4** pts, int* count, int64_t* dropped);
 int seg_device(const ddlo_seg* s);
 gicp_status seg_get_params(const ddlo_seg* s, ddlo_seg_params* out);
 

@@ -587,6 +587,8 @@ struct ddlo_seg {
   int* rec_pin = nullptr;
   unsigned fetched = 0;
   int replayed = 0, longest_prefix = 0;
+  // the tracks' pixel lists (seg_tracks.hip), created by the first ddlo_seg_tracks_sync
+  SegTracks* tracks = nullptr;
 };
 
 // the pinned record: the ints and the first averages in one copy
@@ -674,6 +676,7 @@ gicp_status ddlo_seg_destroy(ddlo_seg* s) {
   if (s->rec_pin) (void)hipHostFree(s->rec_pin);
   s->obj_stage.release();
   s->drop_stage.release();
+  seg_tracks_free(s->tracks);
   (void)hipStreamDestroy(s->s);
   delete s;
   return GICP_OK;
@@ -923,6 +926,54 @@ gicp_status seg_objects_vec(ddlo_seg* o, float max_dim_ratio, std::vector<ddlo_s
 
 gicp_status seg_static_cloud_dev(ddlo_seg* o, const int32_t* remove_ids, size_t n_remove, const float centre[3],
                                  double crop_size, double leaf, const float4** pts, int* count) {
+  return seg_static_cloud_with(o, remove_ids, n_remove, centre, crop_size, leaf, pts, count, nullptr);
+}
+
+gicp_status seg_tracks_view(ddlo_seg* o, SegTrackView* v, bool with_csr) {
+  if (!o || !v) return fail(GICP_EINVAL, "null argument");
+  v->device = o->device;
+  v->stream = o->s;
+  v->npix = o->p.rows * o->p.cols;
+  v->have = o->have;
+  v->segments = o->have ? o->last.segments : 0;
+  v->slot = &o->tracks;
+  v->d_off = v->d_pix = nullptr;
+  v->len.assign((size_t)v->segments + 1, 0);
+  const int L = v->segments;
+  if (L <= 0 || !with_csr) return GICP_OK;
+  HIP_TRY(hipSetDevice(o->device));
+  if (o->labelling == DDLO_SEG_LABEL_DEVICE) {
+    v->d_off = o->ldev.off();
+    v->d_pix = o->ldev.pixels();
+    if (o->have_objects) {   // the object records carry every segment's length
+      for (int l = 1; l <= L; ++l) v->len[l] = o->objects[(size_t)l - 1].num_points;
+    } else {
+      std::vector<int> off((size_t)L + 2);
+      HIP_TRY(hipMemcpyAsync(off.data(), o->ldev.off(), sizeof(int) * off.size(), hipMemcpyDeviceToHost, o->s));
+      HIP_TRY(hipStreamSynchronize(o->s));
+      for (int l = 1; l <= L; ++l) v->len[l] = off[l + 1] - off[l];
+    }
+    return GICP_OK;
+  }
+  const std::vector<int>& off = o->work.seg_off;
+  const size_t noff = (size_t)L + 2, npix = (size_t)off[L + 1];
+  if (!o->have_objects) {   // the upload run_objects makes for k_seg_objects has not happened for this scan
+    std::vector<int> joined(noff + npix);
+    std::memcpy(joined.data(), off.data(), sizeof(int) * noff);
+    if (npix) std::memcpy(joined.data() + noff, o->work.seg_pix.data(), sizeof(int) * npix);
+    HIP_TRY(o->dcsr.ensure(sizeof(int) * joined.size()));
+    HIP_TRY(hipMemcpyAsync(o->dcsr.p, joined.data(), sizeof(int) * joined.size(), hipMemcpyHostToDevice, o->s));
+    HIP_TRY(hipStreamSynchronize(o->s));
+  }
+  v->d_off = o->dcsr.as<int>();
+  v->d_pix = o->dcsr.as<int>() + noff;
+  for (int l = 1; l <= L; ++l) v->len[l] = off[l + 1] - off[l];
+  return GICP_OK;
+}
+
+gicp_status seg_static_cloud_with(ddlo_seg* o, const int32_t* remove_ids, size_t n_remove, const float centre[3],
+                                  double crop_size, double leaf, const float4** pts, int* count,
+                                  const SegDropHook* more) {
   if (!o || !pts || !count || !centre || (!remove_ids && n_remove)) return fail(GICP_EINVAL, "invalid argument");
   if (!o->have) return fail(GICP_EINVAL, "no processed scan");
   const int L = o->last.segments;
@@ -968,6 +1019,8 @@ gicp_status seg_static_cloud_dev(ddlo_seg* o, const int32_t* remove_ids, size_t 
     k_static_drop<<<cdiv_s((long)ndrop, 256), 256, 0, o->s>>>(o->ddrop.as<int>(), (int)ndrop, o->f4.as<float4>());
   }
   HIP_TRY(hipGetLastError());
+  if (more && *more)
+    if (gicp_status st = (*more)(o->s, o->f4.as<float4>(), n)) return st;
   const CropCentre cc{centre[0], centre[1], centre[2]};
   const bool crop = crop_size > 0;
   int m = -1;

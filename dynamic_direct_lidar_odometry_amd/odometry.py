@@ -92,6 +92,8 @@ def _lib():
             "ddlo_dynamic_default_params": (I, [C.POINTER(DynamicParams)]),
             "ddlo_odom_process_dynamic": (I, [P, P, P, S, C.POINTER(DynamicParams), NONSTATIC_FN, P,
                                               C.POINTER(OdomResult), C.POINTER(SegResult)]),
+            "ddlo_odom_process_tracked": (I, [P, P, P, P, P, S, D, C.POINTER(DynamicParams), C.POINTER(OdomResult),
+                                              C.POINTER(SegResult), P]),
             "ddlo_odom_submap": (I, [P, P, S, C.POINTER(S)]),
             "ddlo_odom_ctx": (I, [P, I, C.POINTER(P)]),
             "ddlo_preprocess": (I, [I, P, S, S, D, D, P, S, C.POINTER(S)]),
@@ -197,6 +199,24 @@ class Odometry:
         _check(st)
         seg.last = sr
         return r, sr
+
+    def process_tracked(self, seg: Segmentation, tracker, scan, stamp: float, map=None,
+                        params: DynamicParams | None = None):
+        """ddlo_odom_process_tracked: process_dynamic with the tracker (tracking.Tracker) on board: its
+        UNDEFINED and DYNAMIC tracks' pixel lists, stale ones included, are cut out of the keyframe; with a
+        map (mapping.Map) the boxes of tracks that turned dynamic are cleared from it and new keyframes
+        added.  stamp: the scan's time in seconds.  Returns (OdomResult, SegResult, TrackResult)."""
+        from .tracking import TrackResult
+        a = np.ascontiguousarray(scan, np.float32)
+        if a.ndim != 2 or a.shape[0] != seg.params.rows * seg.params.cols or a.shape[1] < 3:
+            raise ValueError("scan must be (rows*cols, >=3)")
+        r, sr, tr = OdomResult(), SegResult(), TrackResult()
+        _check(self.L.ddlo_odom_process_tracked(self.h, seg.h, tracker.h, map.h if map is not None else None, _ptr(a),
+                                                a.shape[1] * 4, float(stamp), C.byref(params) if params is not None else None,
+                                                C.byref(r), C.byref(sr), C.byref(tr)))
+        seg.last = sr
+        tracker.last = tr
+        return r, sr, tr
 
     def keyframe_points(self, k: int) -> np.ndarray:
         """World-frame points of keyframe k (after the submap voxel filter), (n, 3) float32."""

@@ -106,6 +106,10 @@ def _lib():
             "ddlo_seg_objects": (I, [P, F, P, S, C.POINTER(S)]),
             "ddlo_seg_objects_from": (I, [I, P, S, I, I, P, P, S, F, P, S, C.POINTER(S)]),
             "ddlo_seg_static_cloud": (I, [P, P, S, P, C.c_double, C.c_double, P, S, C.POINTER(S)]),
+            "ddlo_seg_tracks_sync": (I, [P, P, P, S, P, S]),
+            "ddlo_seg_static_cloud_tracks": (I, [P, P, S, P, C.c_double, C.c_double, P, S, C.POINTER(S)]),
+            "ddlo_seg_track_indices": (I, [P, C.c_int32, P, S, C.POINTER(S)]),
+            "ddlo_seg_tracks_stats": (I, [P, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -304,3 +308,39 @@ class Segmentation:
         out = np.zeros((max(n.value, 1), 3), np.float32)
         _check(self.L.ddlo_seg_static_cloud(*args, _ptr(out), out.shape[0], C.byref(n)))
         return out[:n.value]
+
+    def tracks_sync(self, set_pairs=(), dead_ids=()):
+        """ddlo_seg_tracks_sync: set_pairs = (track id, segment id of the last process()) pairs whose lists
+        are (re)set; dead_ids release theirs; every other track keeps its list."""
+        pairs = np.ascontiguousarray(list(set_pairs), np.int32).reshape(-1, 2)
+        tid = np.ascontiguousarray(pairs[:, 0])
+        sid = np.ascontiguousarray(pairs[:, 1])
+        dead = np.ascontiguousarray(dead_ids, np.int32).reshape(-1)
+        _check(self.L.ddlo_seg_tracks_sync(self.h, _ptr(tid) if tid.size else None, _ptr(sid) if sid.size else None,
+                                           tid.size, _ptr(dead) if dead.size else None, dead.size))
+
+    def static_cloud_tracks(self, track_ids=(), centre=(0.0, 0.0, 0.0), crop_size: float = 0.0, leaf: float = 0.0):
+        """static_cloud with the union of the listed tracks' pixel lists (stale ones included) removed
+        from the last scan; (m, 3) float32."""
+        ids = np.ascontiguousarray(track_ids, np.int32).reshape(-1)
+        c = np.ascontiguousarray(centre, np.float32).reshape(3)
+        n = C.c_size_t()
+        args = (self.h, _ptr(ids) if ids.size else None, ids.size, _ptr(c), float(crop_size), float(leaf))
+        _check(self.L.ddlo_seg_static_cloud_tracks(*args, None, 0, C.byref(n)))
+        out = np.zeros((max(n.value, 1), 3), np.float32)
+        _check(self.L.ddlo_seg_static_cloud_tracks(*args, _ptr(out), out.shape[0], C.byref(n)))
+        return out[:n.value]
+
+    def track_indices(self, track_id: int) -> np.ndarray:
+        """The pixel list a track holds (getIndices of one filter), ascending row-major indices."""
+        n = C.c_size_t()
+        _check(self.L.ddlo_seg_track_indices(self.h, int(track_id), None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), np.int32)
+        _check(self.L.ddlo_seg_track_indices(self.h, int(track_id), _ptr(out), out.size, C.byref(n)))
+        return out[:n.value]
+
+    def tracks_stats(self):
+        """(lists held, indices held, capacity of the pool buffer in use)."""
+        a, b, c = C.c_int32(), C.c_int64(), C.c_int64()
+        _check(self.L.ddlo_seg_tracks_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value

@@ -20,9 +20,9 @@
  *
  * Not restated (outside the GICP path): ROS I/O, IMU gravity
  * alignment, the organized-cloud row/col downsampling filter (odom.cc:902-906),
- * the object tracker itself (trackDetections and the bounding-box Kalman
- * filter: its verdict enters through ddlo_nonstatic_fn), publishing and
- * trajectory files.
+ * publishing and trajectory files.  The object tracker (trackDetections and
+ * the bounding-box Kalman filter) is ddlo_track.h: ddlo_odom_process_tracked
+ * runs it; ddlo_odom_process_dynamic takes a verdict through ddlo_nonstatic_fn.
  */
 #ifndef DDLO_ODOM_H
 #define DDLO_ODOM_H
@@ -129,6 +129,32 @@ typedef int (*ddlo_nonstatic_fn)(void* user, const ddlo_seg_object* objs, size_t
 gicp_status ddlo_odom_process_dynamic(struct ddlo_odom* o, struct ddlo_seg* seg, const float* xyz, size_t stride_bytes,
                                       const ddlo_dynamic_params* dp, ddlo_nonstatic_fn decide, void* user,
                                       ddlo_odom_result* res, ddlo_seg_result* seg_res);
+/* ddlo_odom_process_dynamic with the tracker on board (ddlo_track.h) instead
+ * of a callback: scans in; poses, static keyframes and, with a map, a map
+ * without moving things out.  On a TRACKED frame, in this order: the objects;
+ * dt = stamp - time_prev_ (trackDetections, detection.cpp:820-832; time_prev_
+ * starts at 0 and advances only on TRACKED frames); ddlo_track_update;
+ * ddlo_seg_tracks_sync with the tracks this frame's detections updated or
+ * created and the erased ones; then updateKeyframes on ddlo_seg_static_cloud_tracks
+ * of every track whose status is UNDEFINED or DYNAMIC, which is the union the
+ * reference removes (odom.cc:867-892, tracking.cpp:192-208): a track that was
+ * not matched this frame still removes the pixels of the scan it last matched.
+ * map (may be NULL): the box histories of the tracks that turned dynamic go
+ * to ddlo_map_clear_boxes first; if a keyframe was added,
+ * ddlo_map_add_odom_keyframe follows; that includes keyframe 0, made on the
+ * FIRST frame (MapNode receives the first keyframe as every other).  INIT,
+ * FIRST and SKIPPED frames touch neither the tracker nor the lists and zero
+ * *seg_res and *track_res (both optional).  stamp: the scan's time in seconds.
+ * The tracker advances before the lists and the map do: after an error return
+ * the driver is unusable, as after ddlo_odom_process, and the tracker and the
+ * segmentation's lists no longer agree: destroy them with it. */
+struct ddlo_track;
+struct ddlo_map;
+struct ddlo_track_result;
+gicp_status ddlo_odom_process_tracked(struct ddlo_odom* o, struct ddlo_seg* seg, struct ddlo_track* track,
+                                      struct ddlo_map* map, const float* xyz, size_t stride_bytes, double stamp,
+                                      const ddlo_dynamic_params* dp, ddlo_odom_result* res, ddlo_seg_result* seg_res,
+                                      struct ddlo_track_result* track_res);
 /* Keyframe indices of the current submap (sorted, submap_kf_idx_prev_). */
 gicp_status ddlo_odom_submap(const struct ddlo_odom* o, int32_t* idx, size_t cap, size_t* n);
 /* The S2S (which = 0) or S2M (which = 1) GICP context, for the gicp_* getters

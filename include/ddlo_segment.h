@@ -28,10 +28,15 @@
  *                      pixels of the non-static objects, cropped around the
  *                      pose and voxel-filtered, on the device
  *
+ *   ddlo_seg_tracks_sync / ddlo_seg_static_cloud_tracks / ddlo_seg_track_indices
+ *                      the pixel lists the tracker's filters keep from the scan
+ *                      they last matched (bounding_box_filter.cpp:69,133-136),
+ *                      on the device, and the scan without them (ddlo_seg_tracks.h)
+ *
  * The tracker that decides which objects are static (trackDetections, the
- * bounding-box Kalman filter), visualisation and evaluation are not restated:
- * the caller decides (ddlo_odom_process_dynamic takes that verdict as a
- * callback, ddlo_odom.h).
+ * bounding-box Kalman filter) is ddlo_track.h; ddlo_odom_process_tracked
+ * (ddlo_odom.h) runs it, ddlo_odom_process_dynamic takes a caller's verdict
+ * as a callback.  Visualisation and evaluation are not restated.
  *
  * Eigenvector convention of the boxes.  getObject takes the principal axes of
  * a segment's (x, y) covariance from Eigen's SelfAdjointEigenSolver, whose
@@ -140,5 +145,7 @@ gicp_status ddlo_seg_label(const ddlo_seg_params* p, const float* range, const f
 #include "ddlo_seg_objects.h"
 /* ddlo_seg_set_labelling, ddlo_seg_get_labelling, ddlo_seg_label_device, ddlo_seg_labelling_stats */
 #include "ddlo_seg_label.h"
+/* ddlo_seg_tracks_sync, ddlo_seg_static_cloud_tracks, ddlo_seg_track_indices, ddlo_seg_tracks_stats */
+#include "ddlo_seg_tracks.h"
 
 #endif /* DDLO_SEGMENT_H */
