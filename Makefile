@@ -10,8 +10,10 @@ LIBDIR := $(PKG)/_lib
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function
 # the hot path, one file per stage (K1 .. K6), then the other translation units
 STAGES := index_build covariance corr_search moments outputs
-SRCS := $(STAGES) knn_tasks nftree cellgrid tietree capi preprocess odom segment seg_label seg_tracks map track
-OBJS := $(SRCS:%=$(LIBDIR)/%.o)
+SRCS := $(STAGES) knn_tasks nftree cellgrid tietree capi preprocess odom segment seg_label seg_tracks seg_classes map track
+# host-only translation units (.cpp), compiled as the others are so that they share runtime.hpp
+HOST_SRCS := eval
+OBJS := $(SRCS:%=$(LIBDIR)/%.o) $(HOST_SRCS:%=$(LIBDIR)/%.o)
 
 all: lib oracle facade raycast
 
@@ -21,6 +23,10 @@ lib: $(LIBDIR)/libddlo_gicp.so
 $(LIBDIR)/%.o: $(CSRC)/%.hip
 	@mkdir -p $(@D)
 	$(HIPCC) $(HIPFLAGS) -MMD -MP -c $< -o $@
+
+$(LIBDIR)/%.o: $(CSRC)/%.cpp
+	@mkdir -p $(@D)
+	$(HIPCC) $(HIPFLAGS) -x hip -MMD -MP -c $< -o $@
 
 -include $(OBJS:.o=.d)
 
@@ -71,8 +77,11 @@ $(eval $(call VARIANT,covprof,-DDDLO_COV_PROF -DDDLO_DEV,covariance))
 $(LIBDIR)/dev/%.o: $(CSRC)/%.hip
 	@mkdir -p $(@D)
 	$(HIPCC) $(HIPFLAGS) -DDDLO_DEV -MMD -MP -c $< -o $@
-$(LIBDIR)/dev/libddlo_gicp.so: $(SRCS:%=$(LIBDIR)/dev/%.o)
+$(LIBDIR)/dev/%.o: $(CSRC)/%.cpp
+	@mkdir -p $(@D)
+	$(HIPCC) $(HIPFLAGS) -DDDLO_DEV -x hip -MMD -MP -c $< -o $@
+$(LIBDIR)/dev/libddlo_gicp.so: $(SRCS:%=$(LIBDIR)/dev/%.o) $(HOST_SRCS:%=$(LIBDIR)/dev/%.o)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 dev: $(LIBDIR)/dev/libddlo_gicp.so
 .PHONY: dev
--include $(SRCS:%=$(LIBDIR)/dev/%.d)
+-include $(SRCS:%=$(LIBDIR)/dev/%.d) $(HOST_SRCS:%=$(LIBDIR)/dev/%.d)

@@ -1214,6 +1214,13 @@ gicp_status ddlo_odom_process_tracked(ddlo_odom* o, ddlo_seg* seg, ddlo_track* t
   return process_scan(o, xyz, (size_t)sp.rows * sp.cols, stride, res, &d);
 }
 
+gicp_status ddlo_odom_classify(ddlo_seg* seg, const ddlo_track* track, ddlo_seg_class_counts* counts) {
+  if (!seg || !track) return fail(GICP_EINVAL, "null argument");
+  std::vector<int32_t> ids, status;
+  track_live(track, ids, status);
+  return ddlo_seg_classify(seg, ids.data(), status.data(), ids.size(), counts);
+}
+
 gicp_status ddlo_odom_keyframe_points(const ddlo_odom* o, int k, float* xyz, size_t cap, size_t* n) {
   if (!o || !n || (!xyz && cap) || k < 0 || k >= (int)o->keyframes.size()) return fail(GICP_EINVAL, "invalid argument");
   const Keyframe& kf = *o->keyframes[k];

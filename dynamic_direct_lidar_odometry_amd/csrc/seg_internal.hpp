@@ -52,6 +52,35 @@ gicp_status seg_tracks_view(ddlo_seg* s, SegTrackView* v, bool with_csr);
 // leaves it; *dropped (optional) = the sum of the removed lists' lengths
 gicp_status seg_static_cloud_tracks_dev(ddlo_seg* s, const int32_t* track_ids, size_t n, const float centre[3],
                                         double crop_size, double leaf, const float4** pts, int* count, int64_t* dropped);
+// the pool ranges (offset, length) of the lists of the tracks in track_ids,
+// one per id in their order, and the pool buffer in use; a track id that holds
+// no list is GICP_EINVAL.  No device work.
+gicp_status seg_tracks_ranges(ddlo_seg* s, const int32_t* track_ids, size_t n, std::vector<int2>* ranges,
+                              const int** pool);
+
+// The per-pixel classes (seg_classes.hip) live in the segmentation handle;
+// what they need of it: the scan as ddlo_seg_process saw it (never the packed
+// copy ddlo_seg_static_cloud* writes NaN over), the device ground image, and
+// a serial that changes with every scan handed in.
+struct SegClasses;
+void seg_classes_free(SegClasses* c);
+struct SegClassView {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  int rows = 0, cols = 0, ground_rows = 0;
+  bool have = false;                    // a scan was processed
+  unsigned long long serial = 0;        // of the scan in raw
+  const unsigned char* raw = nullptr;   // x, y, z floats first, stride bytes apart
+  size_t stride = 0;
+  const signed char* ground = nullptr;  // ground_mat_
+  SegClasses** slot = nullptr;
+};
+gicp_status seg_classes_view(ddlo_seg* s, SegClassView* v);
+// ddlo_seg_frame_clouds' results as they lie on the device after it (ground,
+// non-static, dynamic, static: float4, w = 0), valid until the next
+// ddlo_seg_classify on s; complete when the call returns.
+gicp_status seg_frame_clouds_dev(ddlo_seg* s, const float4* pts[4], int count[4]);
+
 int seg_device(const ddlo_seg* s);
 gicp_status seg_get_params(const ddlo_seg* s, ddlo_seg_params* out);
 

@@ -192,6 +192,22 @@ gicp_status tracks_sync(ddlo_seg* s, const int32_t* track_ids, const int32_t* se
 
 }  // namespace
 
+gicp_status seg_tracks_ranges(ddlo_seg* s, const int32_t* track_ids, size_t n, std::vector<int2>* ranges,
+                              const int** pool) {
+  if (!s || !ranges || !pool || (n && !track_ids)) return fail(GICP_EINVAL, "invalid argument");
+  SegTrackView v;
+  if (gicp_status st = seg_tracks_view(s, &v, false)) return st;
+  const SegTracks* t = *v.slot;
+  ranges->clear();
+  for (size_t i = 0; i < n; ++i) {
+    const Live* l = t ? t->find(track_ids[i]) : nullptr;
+    if (!l) return fail(GICP_EINVAL, "a track to classify holds no list");
+    ranges->push_back(make_int2(l->off, l->len));
+  }
+  *pool = t ? t->pool[t->cur].as<int>() : nullptr;
+  return GICP_OK;
+}
+
 gicp_status seg_static_cloud_tracks_dev(ddlo_seg* s, const int32_t* track_ids, size_t n, const float centre[3],
                                         double crop_size, double leaf, const float4** pts, int* count,
                                         int64_t* dropped) {

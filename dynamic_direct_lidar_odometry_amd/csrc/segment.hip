@@ -589,6 +589,10 @@ struct ddlo_seg {
   int replayed = 0, longest_prefix = 0;
   // the tracks' pixel lists (seg_tracks.hip), created by the first ddlo_seg_tracks_sync
   SegTracks* tracks = nullptr;
+  // the per-pixel classes (seg_classes.hip), created by the first ddlo_seg_classify;
+  // scan_serial: counts the scans handed in, so that a class image is known to be of the last one
+  SegClasses* classes = nullptr;
+  unsigned long long scan_serial = 0;
 };
 
 // the pinned record: the ints and the first averages in one copy
@@ -677,6 +681,7 @@ gicp_status ddlo_seg_destroy(ddlo_seg* s) {
   s->obj_stage.release();
   s->drop_stage.release();
   seg_tracks_free(s->tracks);
+  seg_classes_free(s->classes);
   (void)hipStreamDestroy(s->s);
   delete s;
   return GICP_OK;
@@ -691,6 +696,7 @@ static gicp_status seg_run(ddlo_seg* o, const float* xyz_t, size_t stride, const
   HIP_TRY(hipSetDevice(o->device));
   o->have = false;
   o->have_objects = false;
+  ++o->scan_serial;
   const size_t raw_sz = (n - 1) * stride + 12;
   HIP_TRY(o->raw.ensure(raw_sz));
   o->raw_stride = stride;
@@ -896,6 +902,7 @@ gicp_status seg_stage_input(ddlo_seg* o, float4** buf, int* npix) {
   const size_t n = (size_t)o->p.rows * o->p.cols;
   HIP_TRY(hipSetDevice(o->device));
   o->have = false;   // the scan in raw is no longer the one the images belong to
+  ++o->scan_serial;
   HIP_TRY(o->raw.ensure(sizeof(float4) * n));
   *buf = o->raw.as<float4>();
   *npix = (int)n;
@@ -968,6 +975,22 @@ gicp_status seg_tracks_view(ddlo_seg* o, SegTrackView* v, bool with_csr) {
   v->d_off = o->dcsr.as<int>();
   v->d_pix = o->dcsr.as<int>() + noff;
   for (int l = 1; l <= L; ++l) v->len[l] = off[l + 1] - off[l];
+  return GICP_OK;
+}
+
+gicp_status seg_classes_view(ddlo_seg* o, SegClassView* v) {
+  if (!o || !v) return fail(GICP_EINVAL, "null argument");
+  v->device = o->device;
+  v->stream = o->s;
+  v->rows = o->p.rows;
+  v->cols = o->p.cols;
+  v->ground_rows = o->p.ground_rows;
+  v->have = o->have;
+  v->serial = o->scan_serial;
+  v->raw = o->raw.as<unsigned char>();
+  v->stride = o->raw_stride;
+  v->ground = o->ground.as<signed char>();
+  v->slot = &o->classes;
   return GICP_OK;
 }
 

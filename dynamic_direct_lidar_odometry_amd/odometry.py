@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import GicpError, GicpParams, GicpResult, _ptr, load
-from .segmentation import OBJECT_DTYPE, SegObject, SegResult, Segmentation
+from .segmentation import OBJECT_DTYPE, ClassCounts, SegObject, SegResult, Segmentation
 
 __all__ = ["OdomParams", "OdomResult", "DynamicParams", "NONSTATIC_FN", "Odometry", "default_odom_params",
            "default_dynamic_params", "preprocess", "median_range", "convex_hull", "concave_hull", "TRACKED", "FIRST", "SKIPPED", "INIT"]
@@ -94,6 +94,7 @@ def _lib():
                                               C.POINTER(OdomResult), C.POINTER(SegResult)]),
             "ddlo_odom_process_tracked": (I, [P, P, P, P, P, S, D, C.POINTER(DynamicParams), C.POINTER(OdomResult),
                                               C.POINTER(SegResult), P]),
+            "ddlo_odom_classify": (I, [P, P, C.POINTER(ClassCounts)]),
             "ddlo_odom_submap": (I, [P, P, S, C.POINTER(S)]),
             "ddlo_odom_ctx": (I, [P, I, C.POINTER(P)]),
             "ddlo_preprocess": (I, [I, P, S, S, D, D, P, S, C.POINTER(S)]),
@@ -217,6 +218,14 @@ class Odometry:
         seg.last = sr
         tracker.last = tr
         return r, sr, tr
+
+    def classify(self, seg: Segmentation, tracker) -> ClassCounts:
+        """ddlo_odom_classify: the classes of the last scan's pixels from the tracker's live filters, after a
+        process_tracked that returned TRACKED.  Read them with seg.class_image(), seg.class_indices(),
+        seg.frame_clouds().  Returns the counts."""
+        c = ClassCounts()
+        _check(self.L.ddlo_odom_classify(seg.h, tracker.h, C.byref(c)))
+        return c
 
     def keyframe_points(self, k: int) -> np.ndarray:
         """World-frame points of keyframe k (after the submap voxel filter), (n, 3) float32."""

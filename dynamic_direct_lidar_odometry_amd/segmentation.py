@@ -18,10 +18,15 @@ import numpy as np
 from . import GicpError, _ptr, load
 
 __all__ = ["SegParams", "SegResult", "SegObject", "OBJECT_DTYPE", "Segmentation", "default_seg_params",
-           "yaml_seg_params", "label_components", "label_components_device", "objects_from", "LABELLING", "EXCLUDED", "UNLABELLED", "REJECTED"]
+           "yaml_seg_params", "label_components", "label_components_device", "objects_from", "LABELLING", "EXCLUDED", "UNLABELLED", "REJECTED",
+           "ClassCounts", "FrameClouds", "CLS_VALID", "CLS_GROUND", "CLS_UNDEFINED", "CLS_STATIC", "CLS_DYNAMIC",
+           "CLS_NON_STATIC"]
 
 EXCLUDED, UNLABELLED, REJECTED = -1, 0, 999999
 LABELLING = {"host": 0, "device": 1}   # DDLO_SEG_LABEL_*
+# DDLO_CLS_*: the bits of the class image (include/ddlo_seg_classes.h)
+CLS_VALID, CLS_GROUND, CLS_UNDEFINED, CLS_STATIC, CLS_DYNAMIC = 1, 2, 4, 8, 16
+CLS_NON_STATIC = CLS_UNDEFINED | CLS_DYNAMIC
 
 
 class SegParams(C.Structure):
@@ -76,6 +81,31 @@ class SegObject(C.Structure):
     ]
 
 
+class ClassCounts(C.Structure):
+    """ddlo_seg_class_counts: pixels per class bit; non_static = UNDEFINED or DYNAMIC; static_points = VALID
+    and not non-static."""
+    _fields_ = [(k, C.c_int32) for k in ("valid", "ground", "undefined", "static_tracks", "dynamic", "non_static",
+                                         "static_points", "reserved")]
+
+
+class _CloudOut(C.Structure):
+    _fields_ = [("xyz", C.c_void_p), ("cap", C.c_size_t), ("n", C.c_size_t)]
+
+
+class _FrameCloudsOut(C.Structure):
+    _fields_ = [(k, _CloudOut) for k in ("ground", "non_static", "dynamic", "static_points")]
+
+
+class FrameClouds:
+    """applySegmentation's four clouds of one frame, each (m, 3) float32 in ascending pixel order."""
+
+    def __init__(self, ground, non_static, dynamic, static_points):
+        self.ground, self.non_static, self.dynamic, self.static_points = ground, non_static, dynamic, static_points
+
+    def __iter__(self):
+        return iter((self.ground, self.non_static, self.dynamic, self.static_points))
+
+
 # the same layout as a numpy structured type (objects() returns such an array)
 OBJECT_DTYPE = np.dtype([("id", np.int32), ("num_points", np.int32), ("state", np.float32, 7),
                          ("axis", np.float32, 2), ("density", np.float32), ("avg_residuum", np.float64)], align=True)
@@ -110,6 +140,10 @@ def _lib():
             "ddlo_seg_static_cloud_tracks": (I, [P, P, S, P, C.c_double, C.c_double, P, S, C.POINTER(S)]),
             "ddlo_seg_track_indices": (I, [P, C.c_int32, P, S, C.POINTER(S)]),
             "ddlo_seg_tracks_stats": (I, [P, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+            "ddlo_seg_classify": (I, [P, P, P, S, C.POINTER(ClassCounts)]),
+            "ddlo_seg_class_image": (I, [P, P]),
+            "ddlo_seg_class_indices": (I, [P, I, I, P, S, C.POINTER(S)]),
+            "ddlo_seg_frame_clouds": (I, [P, C.POINTER(_FrameCloudsOut)]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -344,3 +378,43 @@ class Segmentation:
         a, b, c = C.c_int32(), C.c_int64(), C.c_int64()
         _check(self.L.ddlo_seg_tracks_stats(self.h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
+
+    def classify(self, tracks=()) -> ClassCounts:
+        """ddlo_seg_classify: tracks = (track id, status 0..2) pairs; the class image of the last process():
+        VALID and GROUND from the scan, the status bit of every listed track on its list's pixels (stale lists
+        included).  Returns the counts."""
+        pairs = np.ascontiguousarray(list(tracks), np.int32).reshape(-1, 2)
+        tid = np.ascontiguousarray(pairs[:, 0])
+        st = np.ascontiguousarray(pairs[:, 1])
+        c = ClassCounts()
+        _check(self.L.ddlo_seg_classify(self.h, _ptr(tid) if tid.size else None, _ptr(st) if st.size else None,
+                                        tid.size, C.byref(c)))
+        return c
+
+    def class_image(self) -> np.ndarray:
+        """The class image of the last classify(): (rows, cols) uint8 of CLS_* bits."""
+        img = np.empty((self.params.rows, self.params.cols), np.uint8)
+        _check(self.L.ddlo_seg_class_image(self.h, _ptr(img)))
+        return img
+
+    def class_indices(self, any_bits: int, none_bits: int = 0) -> np.ndarray:
+        """The pixels with at least one bit of any_bits and no bit of none_bits, ascending (int32): an index
+        set as evaluate() writes it; it may name pixels whose current point is not VALID (stale lists)."""
+        out = np.empty(self.params.rows * self.params.cols, np.int32)
+        n = C.c_size_t()
+        _check(self.L.ddlo_seg_class_indices(self.h, int(any_bits), int(none_bits), _ptr(out), out.size, C.byref(n)))
+        return out[:n.value].copy()
+
+    def frame_clouds(self) -> FrameClouds:
+        """ddlo_seg_frame_clouds: the ground, non-static, dynamic and static clouds of the last classify()."""
+        o = _FrameCloudsOut()
+        _check(self.L.ddlo_seg_frame_clouds(self.h, C.byref(o)))       # the sizes (the partition runs here)
+        names = ("ground", "non_static", "dynamic", "static_points")
+        bufs = []
+        for k in names:
+            f = getattr(o, k)
+            a = np.zeros((max(f.n, 1), 3), np.float32)
+            f.xyz, f.cap = a.ctypes.data, a.shape[0]
+            bufs.append(a)
+        _check(self.L.ddlo_seg_frame_clouds(self.h, C.byref(o)))       # the copies
+        return FrameClouds(*[a[:getattr(o, k).n] for a, k in zip(bufs, names)])

@@ -155,6 +155,14 @@ gicp_status ddlo_odom_process_tracked(struct ddlo_odom* o, struct ddlo_seg* seg,
                                       struct ddlo_map* map, const float* xyz, size_t stride_bytes, double stamp,
                                       const ddlo_dynamic_params* dp, ddlo_odom_result* res, ddlo_seg_result* seg_res,
                                       struct ddlo_track_result* track_res);
+/* The classes of the last scan's pixels (ddlo_seg_classes.h) from the
+ * tracker's live filters: ddlo_seg_classify with the ids and statuses that
+ * ddlo_track_tracks shows.  Meant to follow a ddlo_odom_process_tracked that
+ * returned DDLO_ODOM_TRACKED (the lists then belong to these filters);
+ * process_tracked itself does not classify: a caller who never asks pays
+ * nothing.  counts optional.  The clouds, index sets and the image are read
+ * with ddlo_seg_frame_clouds, ddlo_seg_class_indices, ddlo_seg_class_image. */
+gicp_status ddlo_odom_classify(struct ddlo_seg* seg, const struct ddlo_track* track, ddlo_seg_class_counts* counts);
 /* Keyframe indices of the current submap (sorted, submap_kf_idx_prev_). */
 gicp_status ddlo_odom_submap(const struct ddlo_odom* o, int32_t* idx, size_t cap, size_t* n);
 /* The S2S (which = 0) or S2M (which = 1) GICP context, for the gicp_* getters

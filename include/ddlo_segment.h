@@ -36,7 +36,16 @@
  * The tracker that decides which objects are static (trackDetections, the
  * bounding-box Kalman filter) is ddlo_track.h; ddlo_odom_process_tracked
  * (ddlo_odom.h) runs it, ddlo_odom_process_dynamic takes a caller's verdict
- * as a callback.  Visualisation and evaluation are not restated.
+ * as a callback.
+ *
+ *   ddlo_seg_classify / ddlo_seg_class_image / ddlo_seg_class_indices / ddlo_seg_frame_clouds
+ *                      the class of every pixel of the frame (ground, the
+ *                      tracks' statuses), applySegmentation's ground, non-static,
+ *                      dynamic and static clouds (odom.cc:859-899) and the index
+ *                      sets evaluate() writes (ddlo_seg_classes.h; the files:
+ *                      ddlo_eval.h)
+ *
+ * Visualisation is not restated.
  *
  * Eigenvector convention of the boxes.  getObject takes the principal axes of
  * a segment's (x, y) covariance from Eigen's SelfAdjointEigenSolver, whose
@@ -147,5 +156,7 @@ gicp_status ddlo_seg_label(const ddlo_seg_params* p, const float* range, const f
 #include "ddlo_seg_label.h"
 /* ddlo_seg_tracks_sync, ddlo_seg_static_cloud_tracks, ddlo_seg_track_indices, ddlo_seg_tracks_stats */
 #include "ddlo_seg_tracks.h"
+/* ddlo_seg_classify, ddlo_seg_class_image, ddlo_seg_class_indices, ddlo_seg_frame_clouds */
+#include "ddlo_seg_classes.h"
 
 #endif /* DDLO_SEGMENT_H */

@@ -21,7 +21,8 @@
  *   - a pair of boxes whose volumes give 0 / 0 has IoU 0 here (the reference's
  *     NaN cost sends its Hungarian solver into an endless recursion:
  *     DESIGN.md §12).
- * Not restated: ROS messages, the marker text, evaluation files.
+ * Not restated: ROS messages, the marker text.  (The evaluation files:
+ * ddlo_eval.h.)
  */
 #ifndef DDLO_TRACK_H
 #define DDLO_TRACK_H
