@@ -522,6 +522,11 @@ struct DynStep {
   ddlo_map* map = nullptr;
   double stamp = 0.0;
   ddlo_track_result* track_res = nullptr;
+  // ddlo_odom_process_*_cloud: the scan is unorganized and reaches the image
+  // through this projection (resolved and checked by the entry)
+  bool cloud = false;
+  ddlo_seg_projection proj{};
+  ddlo_seg_projection_result* proj_res = nullptr;
 };
 
 namespace {
@@ -732,20 +737,29 @@ gicp_status tracked_step(ddlo_odom* o, const DynStep& d) {
 }
 
 // OdomNode::applySegmentation up to the tracker's verdict (odom.cc:853-870),
-// on a tracked frame after propagateS2M: o->up still holds the frame's
-// organized scan (npix points, stride bytes apart)
-gicp_status dynamic_step(ddlo_odom* o, const DynStep& d, int npix, size_t stride) {
-  float4* buf = nullptr;
-  int n = 0;
-  gicp_status st = seg_stage_input(d.seg, &buf, &n);
-  if (st) return st;
-  if (n != npix) return fail(GICP_EINVAL, "scan size != the segmentation's rows x cols");
-  launch_transform_raw(o->s, o->up.as<unsigned char>(), stride, npix, o->T, buf);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(o->s));
+// on a tracked frame after propagateS2M: o->up still holds the frame's scan
+// (npts points, stride bytes apart): organized, rows x cols of them, or
+// (d.cloud) unorganized, projected into the image by the claim and the fill
+gicp_status dynamic_step(ddlo_odom* o, const DynStep& d, int npts, size_t stride) {
   ddlo_seg_params sp;
-  st = seg_get_params(d.seg, &sp);
+  gicp_status st = seg_get_params(d.seg, &sp);
   if (st) return st;
+  const int npix = sp.rows * sp.cols;
+  if (d.cloud) {
+    ddlo_seg_projection_result pr{};
+    st = seg_project_dev(d.seg, o->s, o->up.as<unsigned char>(), stride, npts, o->T, d.proj, &pr);
+    if (st) return st;
+    if (d.proj_res) *d.proj_res = pr;
+  } else {
+    float4* buf = nullptr;
+    int n = 0;
+    st = seg_stage_input(d.seg, &buf, &n);
+    if (st) return st;
+    if (n != npts) return fail(GICP_EINVAL, "scan size != the segmentation's rows x cols");
+    launch_transform_raw(o->s, o->up.as<unsigned char>(), stride, npts, o->T, buf);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(o->s));
+  }
   if (o->resid_cap < (size_t)npix) {
     if (o->resid_pin) (void)hipHostFree(o->resid_pin);
     o->resid_pin = nullptr;
@@ -758,6 +772,10 @@ gicp_status dynamic_step(ddlo_odom* o, const DynStep& d, int npix, size_t stride
   ddlo_seg_result sr{};
   st = seg_process_staged(d.seg, o->T, o->resid_pin, &sr);
   if (st) return st;
+  if (d.cloud) {
+    st = seg_project_commit(d.seg);
+    if (st) return st;
+  }
   if (d.seg_res) *d.seg_res = sr;
   st = seg_objects_vec(d.seg, d.dp.max_dim_ratio, o->dyn_objs);
   if (st) return st;
@@ -1212,6 +1230,51 @@ gicp_status ddlo_odom_process_tracked(ddlo_odom* o, ddlo_seg* seg, ddlo_track* t
   if (seg_res) std::memset(seg_res, 0, sizeof(*seg_res));
   if (track_res) std::memset(track_res, 0, sizeof(*track_res));
   return process_scan(o, xyz, (size_t)sp.rows * sp.cols, stride, res, &d);
+}
+
+// the *_cloud entries' part of a DynStep: the projection resolved and checked before anything runs
+static gicp_status cloud_step(DynStep* d, const ddlo_seg_projection* proj, ddlo_seg_projection_result* proj_res) {
+  d->cloud = true;
+  d->proj_res = proj_res;
+  if (proj_res) std::memset(proj_res, 0, sizeof(*proj_res));
+  return seg_projection_resolve(d->seg, proj, &d->proj);
+}
+
+gicp_status ddlo_odom_process_dynamic_cloud(ddlo_odom* o, ddlo_seg* seg, const float* xyz, size_t stride, size_t n,
+                                            const ddlo_dynamic_params* dp, ddlo_nonstatic_fn decide, void* user,
+                                            const ddlo_seg_projection* proj, ddlo_odom_result* res,
+                                            ddlo_seg_result* seg_res, ddlo_seg_projection_result* proj_res) {
+  if (!o || !seg || (!xyz && n) || !res) return fail(GICP_EINVAL, "null argument");
+  if (seg_device(seg) != o->device) return fail(GICP_EINVAL, "the segmentation lives on another device");
+  DynStep d{seg, {}, decide, user, seg_res};
+  if (dp) d.dp = *dp;
+  else ddlo_dynamic_default_params(&d.dp);
+  if (!(d.dp.theta_max > d.dp.theta_min)) return fail(GICP_EINVAL, "theta_max must exceed theta_min");
+  if (gicp_status st = cloud_step(&d, proj, proj_res)) return st;
+  if (seg_res) std::memset(seg_res, 0, sizeof(*seg_res));
+  return process_scan(o, xyz, n, stride, res, &d);
+}
+
+gicp_status ddlo_odom_process_tracked_cloud(ddlo_odom* o, ddlo_seg* seg, ddlo_track* track, ddlo_map* map,
+                                            const float* xyz, size_t stride, size_t n, double stamp,
+                                            const ddlo_dynamic_params* dp, const ddlo_seg_projection* proj,
+                                            ddlo_odom_result* res, ddlo_seg_result* seg_res, ddlo_track_result* track_res,
+                                            ddlo_seg_projection_result* proj_res) {
+  if (!o || !seg || !track || (!xyz && n) || !res) return fail(GICP_EINVAL, "null argument");
+  if (seg_device(seg) != o->device) return fail(GICP_EINVAL, "the segmentation lives on another device");
+  if (!std::isfinite(stamp)) return fail(GICP_EINVAL, "non-finite stamp");
+  DynStep d{seg, {}, nullptr, nullptr, seg_res};
+  d.track = track;
+  d.map = map;
+  d.stamp = stamp;
+  d.track_res = track_res;
+  if (dp) d.dp = *dp;
+  else ddlo_dynamic_default_params(&d.dp);
+  if (!(d.dp.theta_max > d.dp.theta_min)) return fail(GICP_EINVAL, "theta_max must exceed theta_min");
+  if (gicp_status st = cloud_step(&d, proj, proj_res)) return st;
+  if (seg_res) std::memset(seg_res, 0, sizeof(*seg_res));
+  if (track_res) std::memset(track_res, 0, sizeof(*track_res));
+  return process_scan(o, xyz, n, stride, res, &d);
 }
 
 gicp_status ddlo_odom_classify(ddlo_seg* seg, const ddlo_track* track, ddlo_seg_class_counts* counts) {

@@ -316,6 +316,15 @@ gicp_status seg_frame_clouds_dev(ddlo_seg* s, const float4* pts[4], int count[4]
   return GICP_OK;
 }
 
+gicp_status seg_class_image_dev(ddlo_seg* s, const unsigned char** img) {
+  if (!s || !img) return fail(GICP_EINVAL, "null argument");
+  SegClassView v;
+  SegClasses* c = nullptr;
+  if (gicp_status st = current(s, &v, &c)) return st;
+  *img = c->img.as<unsigned char>();
+  return GICP_OK;
+}
+
 }  // namespace ddlo
 
 using namespace ddlo;

@@ -81,6 +81,34 @@ gicp_status seg_classes_view(ddlo_seg* s, SegClassView* v);
 // ddlo_seg_classify on s; complete when the call returns.
 gicp_status seg_frame_clouds_dev(ddlo_seg* s, const float4* pts[4], int count[4]);
 
+// the class image of the last scan on the device (rows x cols bytes), or
+// GICP_EINVAL as ddlo_seg_class_image; no device work
+gicp_status seg_class_image_dev(ddlo_seg* s, const unsigned char** img);
+
+// The projection of an unorganized cloud (seg_project.hip): its maps and
+// scratch live in the segmentation handle; what they need of it.
+struct SegProject;
+void seg_project_free(SegProject* p);
+struct SegProjView {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  ddlo_seg_params params{};
+  bool have = false;                 // a scan was processed
+  unsigned long long serial = 0;     // of the scan in the handle
+  SegProject** slot = nullptr;
+};
+gicp_status seg_project_view(ddlo_seg* s, SegProjView* v);
+// proj (NULL: the defaults of s) checked and resolved into *out; no device work
+gicp_status seg_projection_resolve(ddlo_seg* s, const ddlo_seg_projection* proj, ddlo_seg_projection* out);
+// Claim and fill: the n points in raw (device memory, stride bytes apart,
+// complete on st) into the segmentation's staged input (seg_stage_input),
+// moved by T; runs on st and waits for it.  *out: the counts.  proj: resolved.
+gicp_status seg_project_dev(ddlo_seg* s, hipStream_t st, const unsigned char* raw, size_t stride, int n, const float T[16],
+                            const ddlo_seg_projection& proj, ddlo_seg_projection_result* out);
+// after the seg_process_staged that followed seg_project_dev: the maps are
+// those of the handle's scan
+gicp_status seg_project_commit(ddlo_seg* s);
+
 int seg_device(const ddlo_seg* s);
 gicp_status seg_get_params(const ddlo_seg* s, ddlo_seg_params* out);
 

@@ -593,6 +593,8 @@ struct ddlo_seg {
   // scan_serial: counts the scans handed in, so that a class image is known to be of the last one
   SegClasses* classes = nullptr;
   unsigned long long scan_serial = 0;
+  // the projection of unorganized clouds (seg_project.hip), created by the first projected scan
+  SegProject* project = nullptr;
 };
 
 // the pinned record: the ints and the first averages in one copy
@@ -682,6 +684,7 @@ gicp_status ddlo_seg_destroy(ddlo_seg* s) {
   s->drop_stage.release();
   seg_tracks_free(s->tracks);
   seg_classes_free(s->classes);
+  seg_project_free(s->project);
   (void)hipStreamDestroy(s->s);
   delete s;
   return GICP_OK;
@@ -991,6 +994,17 @@ gicp_status seg_classes_view(ddlo_seg* o, SegClassView* v) {
   v->stride = o->raw_stride;
   v->ground = o->ground.as<signed char>();
   v->slot = &o->classes;
+  return GICP_OK;
+}
+
+gicp_status seg_project_view(ddlo_seg* o, SegProjView* v) {
+  if (!o || !v) return fail(GICP_EINVAL, "null argument");
+  v->device = o->device;
+  v->stream = o->s;
+  v->params = o->p;
+  v->have = o->have;
+  v->serial = o->scan_serial;
+  v->slot = &o->project;
   return GICP_OK;
 }
 

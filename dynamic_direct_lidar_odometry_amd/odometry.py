@@ -13,7 +13,8 @@ import ctypes as C
 import numpy as np
 
 from . import GicpError, GicpParams, GicpResult, _ptr, load
-from .segmentation import OBJECT_DTYPE, ClassCounts, SegObject, SegResult, Segmentation
+from .segmentation import (OBJECT_DTYPE, ClassCounts, ProjectionParams, ProjectionResult, SegObject, SegResult,
+                           Segmentation)
 
 __all__ = ["OdomParams", "OdomResult", "DynamicParams", "NONSTATIC_FN", "Odometry", "default_odom_params",
            "default_dynamic_params", "preprocess", "median_range", "convex_hull", "concave_hull", "TRACKED", "FIRST", "SKIPPED", "INIT"]
@@ -94,6 +95,12 @@ def _lib():
                                               C.POINTER(OdomResult), C.POINTER(SegResult)]),
             "ddlo_odom_process_tracked": (I, [P, P, P, P, P, S, D, C.POINTER(DynamicParams), C.POINTER(OdomResult),
                                               C.POINTER(SegResult), P]),
+            "ddlo_odom_process_dynamic_cloud": (I, [P, P, P, S, S, C.POINTER(DynamicParams), NONSTATIC_FN, P,
+                                                    C.POINTER(ProjectionParams), C.POINTER(OdomResult),
+                                                    C.POINTER(SegResult), C.POINTER(ProjectionResult)]),
+            "ddlo_odom_process_tracked_cloud": (I, [P, P, P, P, P, S, S, D, C.POINTER(DynamicParams),
+                                                    C.POINTER(ProjectionParams), C.POINTER(OdomResult),
+                                                    C.POINTER(SegResult), P, C.POINTER(ProjectionResult)]),
             "ddlo_odom_classify": (I, [P, P, C.POINTER(ClassCounts)]),
             "ddlo_odom_submap": (I, [P, P, S, C.POINTER(S)]),
             "ddlo_odom_ctx": (I, [P, I, C.POINTER(P)]),
@@ -170,6 +177,9 @@ class Odometry:
         a = np.ascontiguousarray(scan, np.float32)
         if a.ndim != 2 or a.shape[0] != seg.params.rows * seg.params.cols or a.shape[1] < 3:
             raise ValueError("scan must be (rows*cols, >=3)")
+        return self._process_dynamic(seg, a, decide, params, False, None)
+
+    def _process_dynamic(self, seg, a, decide, params, cloud, projection):
         raised = []
 
         def trampoline(_user, objs, n, flags):
@@ -192,14 +202,50 @@ class Odometry:
 
         cb = NONSTATIC_FN(trampoline) if decide is not None else C.cast(None, NONSTATIC_FN)
         r, sr = OdomResult(), SegResult()
-        st = self.L.ddlo_odom_process_dynamic(self.h, seg.h, _ptr(a), a.shape[1] * 4,
-                                              C.byref(params) if params is not None else None, cb, None,
-                                              C.byref(r), C.byref(sr))
+        if cloud:
+            pr = ProjectionResult()
+            st = self.L.ddlo_odom_process_dynamic_cloud(self.h, seg.h, _ptr(a) if a.shape[0] else None, a.shape[1] * 4,
+                                                        a.shape[0], C.byref(params) if params is not None else None,
+                                                        cb, None, C.byref(projection) if projection is not None else None,
+                                                        C.byref(r), C.byref(sr), C.byref(pr))
+        else:
+            st = self.L.ddlo_odom_process_dynamic(self.h, seg.h, _ptr(a), a.shape[1] * 4,
+                                                  C.byref(params) if params is not None else None, cb, None,
+                                                  C.byref(r), C.byref(sr))
         if raised:
             raise raised[0]
         _check(st)
         seg.last = sr
-        return r, sr
+        return (r, sr, pr) if cloud else (r, sr)
+
+    def process_dynamic_cloud(self, seg: Segmentation, points, decide=None, params: DynamicParams | None = None,
+                              projection: ProjectionParams | None = None):
+        """ddlo_odom_process_dynamic_cloud: process_dynamic for an unorganized sensor-frame cloud (n, >=3):
+        every point registers; the image is the cloud's projection (projection None: the defaults of seg's
+        parameters).  Returns (OdomResult, SegResult, ProjectionResult); seg.projection_maps() and, after a
+        classification, seg.point_classes() answer in the indices of points."""
+        a = np.ascontiguousarray(points, np.float32)
+        if a.ndim != 2 or a.shape[1] < 3:
+            raise ValueError("points must be (n, >=3)")
+        return self._process_dynamic(seg, a, decide, params, True, projection)
+
+    def process_tracked_cloud(self, seg: Segmentation, tracker, points, stamp: float, map=None,
+                              params: DynamicParams | None = None, projection: ProjectionParams | None = None):
+        """ddlo_odom_process_tracked_cloud: process_tracked for an unorganized sensor-frame cloud (n, >=3).
+        Returns (OdomResult, SegResult, TrackResult, ProjectionResult)."""
+        from .tracking import TrackResult
+        a = np.ascontiguousarray(points, np.float32)
+        if a.ndim != 2 or a.shape[1] < 3:
+            raise ValueError("points must be (n, >=3)")
+        r, sr, tr, pr = OdomResult(), SegResult(), TrackResult(), ProjectionResult()
+        _check(self.L.ddlo_odom_process_tracked_cloud(
+            self.h, seg.h, tracker.h, map.h if map is not None else None, _ptr(a) if a.shape[0] else None,
+            a.shape[1] * 4, a.shape[0], float(stamp), C.byref(params) if params is not None else None,
+            C.byref(projection) if projection is not None else None, C.byref(r), C.byref(sr), C.byref(tr),
+            C.byref(pr)))
+        seg.last = sr
+        tracker.last = tr
+        return r, sr, tr, pr
 
     def process_tracked(self, seg: Segmentation, tracker, scan, stamp: float, map=None,
                         params: DynamicParams | None = None):

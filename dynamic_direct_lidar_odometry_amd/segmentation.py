@@ -20,7 +20,7 @@ from . import GicpError, _ptr, load
 __all__ = ["SegParams", "SegResult", "SegObject", "OBJECT_DTYPE", "Segmentation", "default_seg_params",
            "yaml_seg_params", "label_components", "label_components_device", "objects_from", "LABELLING", "EXCLUDED", "UNLABELLED", "REJECTED",
            "ClassCounts", "FrameClouds", "CLS_VALID", "CLS_GROUND", "CLS_UNDEFINED", "CLS_STATIC", "CLS_DYNAMIC",
-           "CLS_NON_STATIC"]
+           "CLS_NON_STATIC", "ProjectionParams", "ProjectionResult", "default_projection"]
 
 EXCLUDED, UNLABELLED, REJECTED = -1, 0, 999999
 LABELLING = {"host": 0, "device": 1}   # DDLO_SEG_LABEL_*
@@ -88,6 +88,18 @@ class ClassCounts(C.Structure):
                                          "static_points", "reserved")]
 
 
+class ProjectionParams(C.Structure):
+    """ddlo_seg_projection: elevation of row 0 and the step down to the next row (degrees, > 0), azimuth of
+    column 0, and whether columns grow with atan2(y, x) (+1) or against it (-1)."""
+    _fields_ = [("elev_top_deg", C.c_float), ("elev_res_deg", C.c_float), ("azim0_deg", C.c_float),
+                ("azim_sign", C.c_int32)]
+
+
+class ProjectionResult(C.Structure):
+    """ddlo_seg_projection_result: points = invalid + out_of_view + occupied_pixels + collisions."""
+    _fields_ = [(k, C.c_int32) for k in ("points", "invalid", "out_of_view", "occupied_pixels", "collisions")]
+
+
 class _CloudOut(C.Structure):
     _fields_ = [("xyz", C.c_void_p), ("cap", C.c_size_t), ("n", C.c_size_t)]
 
@@ -144,6 +156,11 @@ def _lib():
             "ddlo_seg_class_image": (I, [P, P]),
             "ddlo_seg_class_indices": (I, [P, I, I, P, S, C.POINTER(S)]),
             "ddlo_seg_frame_clouds": (I, [P, C.POINTER(_FrameCloudsOut)]),
+            "ddlo_seg_default_projection": (I, [C.POINTER(SegParams), C.POINTER(ProjectionParams)]),
+            "ddlo_seg_process_cloud": (I, [P, P, S, S, P, C.POINTER(ProjectionParams), P, C.POINTER(SegResult),
+                                           C.POINTER(ProjectionResult)]),
+            "ddlo_seg_projection_maps": (I, [P, P, P, S, C.POINTER(S)]),
+            "ddlo_seg_point_classes": (I, [P, P, S, C.POINTER(S)]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -163,6 +180,16 @@ def default_seg_params(**kw) -> SegParams:
     p = SegParams()
     _check(_lib().ddlo_seg_default_params(C.byref(p)))
     return p.replace(**kw) if kw else p
+
+
+def default_projection(params: SegParams, **kw) -> ProjectionParams:
+    """ddlo_seg_default_projection: the ring model of params (row 0 at +ang_bottom, the last row at
+    -ang_bottom, column 0 along +x, columns growing with atan2(y, x)): scene.lidar_dirs' model."""
+    q = ProjectionParams()
+    _check(_lib().ddlo_seg_default_projection(C.byref(params), C.byref(q)))
+    for k, v in kw.items():
+        setattr(q, k, v)
+    return q
 
 
 def yaml_seg_params(**kw) -> SegParams:
@@ -288,6 +315,55 @@ class Segmentation:
                                        C.byref(r)))
         self.last = r
         return r
+
+    def process_cloud(self, points, T, residual=None, projection: ProjectionParams | None = None):
+        """ddlo_seg_process_cloud: points (n, >=3) float32, an unorganized SENSOR-frame cloud (n may be 0),
+        projected into the range image (the highest index wins a pixel), moved to the world frame by the pose
+        T and segmented.  projection None: default_projection(self.params).  Returns (SegResult,
+        ProjectionResult)."""
+        a = np.ascontiguousarray(points, np.float32)
+        if a.ndim != 2 or a.shape[1] < 3:
+            raise ValueError("points must be (n, >=3)")
+        Tm = np.ascontiguousarray(T, np.float32).reshape(16)
+        res = None
+        if residual is not None:
+            res = np.ascontiguousarray(residual, np.float32).reshape(-1)
+            if res.size != self.params.rows * self.params.cols:
+                raise ValueError("residual image must have rows x cols pixels")
+        r, pr = SegResult(), ProjectionResult()
+        _check(self.L.ddlo_seg_process_cloud(self.h, _ptr(a) if a.shape[0] else None, a.shape[0], a.shape[1] * 4,
+                                             _ptr(Tm), C.byref(projection) if projection is not None else None,
+                                             None if res is None else _ptr(res), C.byref(r), C.byref(pr)))
+        self.last = r
+        return r, pr
+
+    def projection_maps(self):
+        """The maps of the last projected scan: (winner (rows, cols) int32: the input index whose point the
+        pixel holds, -1 if empty; pixel_of_point (n,) int32: the row-major pixel of every input point, -1 if
+        it was invalid or out of view)."""
+        n = C.c_size_t()
+        _check(self.L.ddlo_seg_projection_maps(self.h, None, None, 0, C.byref(n)))
+        win = np.empty((self.params.rows, self.params.cols), np.int32)
+        pix = np.empty(n.value, np.int32)
+        _check(self.L.ddlo_seg_projection_maps(self.h, _ptr(win), _ptr(pix) if pix.size else None, pix.size,
+                                               C.byref(n)))
+        return win, pix
+
+    def point_classes(self) -> np.ndarray:
+        """ddlo_seg_point_classes: the class byte (CLS_* bits) of every input point of the last projected
+        scan, after a classify(): that of the pixel the point fell into, 0 if it was dropped."""
+        n = C.c_size_t()
+        _check(self.L.ddlo_seg_point_classes(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.uint8)
+        if n.value:
+            _check(self.L.ddlo_seg_point_classes(self.h, _ptr(out), out.size, C.byref(n)))
+        return out
+
+    def point_class_indices(self, any_bits: int, none_bits: int = 0) -> np.ndarray:
+        """The input points with at least one bit of any_bits and no bit of none_bits, ascending (int64):
+        class_indices() in the caller's point indices (a host pass over point_classes())."""
+        b = self.point_classes()
+        return np.flatnonzero(((b & int(any_bits)) != 0) & ((b & int(none_bits)) == 0))
 
     def images(self):
         H, W = self.params.rows, self.params.cols

@@ -155,6 +155,32 @@ gicp_status ddlo_odom_process_tracked(struct ddlo_odom* o, struct ddlo_seg* seg,
                                       struct ddlo_map* map, const float* xyz, size_t stride_bytes, double stamp,
                                       const ddlo_dynamic_params* dp, ddlo_odom_result* res, ddlo_seg_result* seg_res,
                                       struct ddlo_track_result* track_res);
+/* ddlo_odom_process_dynamic and ddlo_odom_process_tracked for an UNORGANIZED
+ * sensor-frame cloud of n points (a Velodyne-style packet stream, a filtered
+ * or merged cloud; ddlo_seg_project.h).  The registration half is
+ * ddlo_odom_process on the same (xyz, n), bit for bit: every point registers,
+ * those the image drops included.  On a TRACKED frame the world-frame
+ * organized scan is not T_ * xyz pixel by pixel but the projection of the
+ * frame's upload: every point's pixel from its sensor-frame elevation and
+ * azimuth, the highest index wins a pixel, T_ * the winner goes into the
+ * image (the same bits the organized entries compute for that point), an
+ * empty pixel is NaN.  Everything after it is what the organized twins do.
+ * proj NULL: ddlo_seg_default_projection of seg's parameters; an invalid
+ * projection is GICP_EINVAL before the scan is touched.  proj_res (optional)
+ * is zeroed on INIT, FIRST and SKIPPED frames, as *seg_res is.  Afterwards
+ * ddlo_seg_projection_maps and, once classified, ddlo_seg_point_classes
+ * answer in the caller's point indices. */
+gicp_status ddlo_odom_process_dynamic_cloud(struct ddlo_odom* o, struct ddlo_seg* seg, const float* xyz,
+                                            size_t stride_bytes, size_t n, const ddlo_dynamic_params* dp,
+                                            ddlo_nonstatic_fn decide, void* user, const ddlo_seg_projection* proj,
+                                            ddlo_odom_result* res, ddlo_seg_result* seg_res,
+                                            ddlo_seg_projection_result* proj_res);
+gicp_status ddlo_odom_process_tracked_cloud(struct ddlo_odom* o, struct ddlo_seg* seg, struct ddlo_track* track,
+                                            struct ddlo_map* map, const float* xyz, size_t stride_bytes, size_t n,
+                                            double stamp, const ddlo_dynamic_params* dp,
+                                            const ddlo_seg_projection* proj, ddlo_odom_result* res,
+                                            ddlo_seg_result* seg_res, struct ddlo_track_result* track_res,
+                                            ddlo_seg_projection_result* proj_res);
 /* The classes of the last scan's pixels (ddlo_seg_classes.h) from the
  * tracker's live filters: ddlo_seg_classify with the ids and statuses that
  * ddlo_track_tracks shows.  Meant to follow a ddlo_odom_process_tracked that

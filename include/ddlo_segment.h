@@ -45,6 +45,12 @@
  *                      sets evaluate() writes (ddlo_seg_classes.h; the files:
  *                      ddlo_eval.h)
  *
+ *   ddlo_seg_process_cloud / ddlo_seg_projection_maps / ddlo_seg_point_classes
+ *                      an unorganized cloud projected to the range image by
+ *                      elevation and azimuth (the loop the reference carries
+ *                      commented out, detection.cpp:341-357), and the way back
+ *                      from pixels to the caller's points (ddlo_seg_project.h)
+ *
  * Visualisation is not restated.
  *
  * Eigenvector convention of the boxes.  getObject takes the principal axes of
@@ -158,5 +164,8 @@ gicp_status ddlo_seg_label(const ddlo_seg_params* p, const float* range, const f
 #include "ddlo_seg_tracks.h"
 /* ddlo_seg_classify, ddlo_seg_class_image, ddlo_seg_class_indices, ddlo_seg_frame_clouds */
 #include "ddlo_seg_classes.h"
+/* ddlo_seg_projection, ddlo_seg_default_projection, ddlo_seg_process_cloud, ddlo_seg_projection_maps,
+   ddlo_seg_point_classes */
+#include "ddlo_seg_project.h"
 
 #endif /* DDLO_SEGMENT_H */
