@@ -162,7 +162,7 @@ struct ddlo_map {
   int size = 0, cap = 0;     // points
   // scratch (device): the upload, its float4 form, the flags and their scan, the voxel filter's, hipcub's, the boxes
   DevBuf up, a, keep, pos, vscratch, cubtmp, boxes;
-  int* pin = nullptr;        // pinned: 16 ints, the count read-backs
+  PinBuf pin;                // pinned: 16 ints, the count read-backs
 };
 
 namespace {
@@ -207,14 +207,14 @@ gicp_status add_points(ddlo_map* m, const float4* in, int n, size_t* added) {
   if (vox) {
     HIP_TRY(m->vscratch.ensure(sizeof(int) * voxel_scratch_ints(n)));
     if (voxel_grid(m->s, in, n, (float)m->p.leaf_size, tail, m->vscratch.as<int>(), m->cubtmp.p, m->cubtmp.bytes, &c, 0.f,
-                   m->pin))
+                   m->pin.as<int>()))
       return fail(GICP_EHIP, "voxel filter scratch too small");
     if (c < 0) vox = false;   // voxel-index overflow: PCL leaves the cloud as it is
   }
   if (!vox) {   // the finite points in input order
     HIP_TRY(m->keep.ensure(sizeof(int) * (size_t)n));
     HIP_TRY(m->pos.ensure(sizeof(int) * (size_t)n));
-    if (crop_box(m->s, in, n, 0.f, tail, m->keep.as<int>(), m->pos.as<int>(), m->cubtmp.p, m->cubtmp.bytes, &c, m->pin,
+    if (crop_box(m->s, in, n, 0.f, tail, m->keep.as<int>(), m->pos.as<int>(), m->cubtmp.p, m->cubtmp.bytes, &c, m->pin.as<int>(),
                  CropCentre(), false))
       return fail(GICP_EHIP, "compaction scratch too small");
   }
@@ -262,10 +262,10 @@ bool pack_box(const ddlo_map_box& b, double margin, float4* aabb, float4* rec) {
 }
 
 // the map's points on the host; leaf > 0: savePcd's voxelised copy
-// (map.cc:169-177), its scratch allocated for the call.  count_only: *count alone.
-gicp_status export_points(ddlo_map* m, double leaf, bool count_only, std::vector<float4>& host, size_t* count) {
+// (map.cc:169-177), its scratch allocated for the call: *count of them, as
+// triples in xyz (room for cap points) unless it is nullptr
+gicp_status export_points(ddlo_map* m, double leaf, float* xyz, size_t cap, size_t* count) {
   *count = 0;
-  host.clear();
   if (m->size == 0) return GICP_OK;
   HIP_TRY(hipSetDevice(m->device));
   const int n = m->size;
@@ -276,19 +276,18 @@ gicp_status export_points(ddlo_map* m, double leaf, bool count_only, std::vector
     HIP_TRY(out.ensure(sizeof(float4) * (size_t)n));
     HIP_TRY(scratch.ensure(sizeof(int) * voxel_scratch_ints(n)));
     HIP_TRY(tmp.ensure(voxel_tmp_bytes(n)));
-    if (voxel_grid(m->s, src, n, (float)leaf, out.as<float4>(), scratch.as<int>(), tmp.p, tmp.bytes, &c, 0.f, m->pin))
+    if (voxel_grid(m->s, src, n, (float)leaf, out.as<float4>(), scratch.as<int>(), tmp.p, tmp.bytes, &c, 0.f,
+                   m->pin.as<int>()))
       return fail(GICP_EHIP, "voxel filter scratch too small");
     HIP_TRY(hipGetLastError());
     if (c < 0) c = n;   // voxel-index overflow: the map as it is
     else src = out.as<float4>();
   }
   *count = (size_t)c;
-  if (!count_only) {
-    host.resize((size_t)c);
-    HIP_TRY(hipMemcpyAsync(host.data(), src, sizeof(float4) * (size_t)c, hipMemcpyDeviceToHost, m->s));
-  }
-  HIP_TRY(hipStreamSynchronize(m->s));   // the scratch goes back to the pool idle
-  return GICP_OK;
+  // either way the stream is waited for: the scratch goes back to the pool idle
+  if (xyz && (size_t)c <= cap) return read_xyz(m->s, src, (size_t)c, xyz);
+  HIP_TRY(hipStreamSynchronize(m->s));
+  return xyz ? fail(GICP_EINVAL, "output capacity too small") : GICP_OK;
 }
 
 }  // namespace
@@ -320,10 +319,9 @@ gicp_status ddlo_map_create(int device, const ddlo_map_params* p, ddlo_map** out
   HIP_TRY(hipSetDevice(device));
   HIP_TRY(stream_pool().acquire(&m->s));
   if (hipEventCreateWithFlags(&m->ev, hipEventDisableTiming) != hipSuccess ||
-      hipHostMalloc((void**)&m->pin, sizeof(int) * 16, hipHostMallocDefault) != hipSuccess ||
+      m->pin.reset(sizeof(int) * 16) != hipSuccess ||
       m->pts.ensure(sizeof(float4) * (size_t)kMapInitialCapacity) != hipSuccess) {
     if (m->ev) (void)hipEventDestroy(m->ev);
-    if (m->pin) (void)hipHostFree(m->pin);
     stream_pool().release(device, m->s);
     return fail(GICP_EHIP, "allocation failed");
   }
@@ -337,7 +335,6 @@ gicp_status ddlo_map_destroy(ddlo_map* m) {
   (void)hipSetDevice(m->device);
   (void)hipStreamSynchronize(m->s);
   if (m->ev) (void)hipEventDestroy(m->ev);
-  if (m->pin) (void)hipHostFree(m->pin);
   stream_pool().release(m->device, m->s);
   delete m;
   return GICP_OK;
@@ -405,7 +402,7 @@ gicp_status ddlo_map_clear_boxes(ddlo_map* m, const ddlo_map_box* boxes, size_t 
     k_map_box_flags<true><<<grid, 256, 0, m->s>>>(m->pts.as<float4>(), n, aabb, rec, nb, m->keep.as<int>());
   int c = 0;
   if (compact_flagged(m->s, m->pts.as<float4>(), n, m->alt.as<float4>(), m->keep.as<int>(), m->pos.as<int>(),
-                      m->cubtmp.p, m->cubtmp.bytes, &c, m->pin))
+                      m->cubtmp.p, m->cubtmp.bytes, &c, m->pin.as<int>()))
     return fail(GICP_EHIP, "compaction scratch too small");
   HIP_TRY(hipGetLastError());
   swap_buf(m->pts, m->alt);
@@ -422,30 +419,15 @@ gicp_status ddlo_map_size(const ddlo_map* m, size_t* n) {
 
 gicp_status ddlo_map_points(ddlo_map* m, double leaf, float* xyz, size_t cap, size_t* n) {
   if (!m || !n || (!xyz && cap)) return fail(GICP_EINVAL, "invalid argument");
-  std::vector<float4> h;
-  gicp_status st = export_points(m, leaf, xyz == nullptr, h, n);
-  if (st || !xyz) return st;
-  if (*n > cap) return fail(GICP_EINVAL, "output capacity too small");
-  for (size_t i = 0; i < h.size(); ++i) {
-    xyz[3 * i] = h[i].x;
-    xyz[3 * i + 1] = h[i].y;
-    xyz[3 * i + 2] = h[i].z;
-  }
-  return GICP_OK;
+  return export_points(m, leaf, xyz, cap, n);
 }
 
 gicp_status ddlo_map_save_pcd(ddlo_map* m, const char* path, double leaf) {
   if (!m || !path) return fail(GICP_EINVAL, "null argument");
-  std::vector<float4> h;
   size_t n = 0;
-  gicp_status st = export_points(m, leaf, false, h, &n);
+  std::vector<float> xyz(3 * (size_t)m->size + 1);   // (the voxelised copy is no larger; + 1: never a null pointer)
+  gicp_status st = export_points(m, leaf, xyz.data(), (size_t)m->size, &n);
   if (st) return st;
-  std::vector<float> xyz(3 * n);
-  for (size_t i = 0; i < n; ++i) {
-    xyz[3 * i] = h[i].x;
-    xyz[3 * i + 1] = h[i].y;
-    xyz[3 * i + 2] = h[i].z;
-  }
   FILE* f = std::fopen(path, "wb");
   if (!f) return fail(GICP_EINVAL, std::string("cannot open ") + path);
   // the header pcl::PCDWriter::writeBinary gives an unorganized cloud of x, y, z

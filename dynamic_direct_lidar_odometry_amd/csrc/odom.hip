@@ -469,8 +469,8 @@ struct ddlo_odom {
   DevBuf up, a, b, keep, pos, vscratch, cubtmp, medtmp, rng, rng_sorted, cat_pts, cat_cov;
   // pinned host memory: [0] the median range of the current scan, [4..19] the
   // voxel / crop count read-back (int)
-  float* median_pin = nullptr;
-  int* count_pin = nullptr;
+  PinBuf median_pin;
+  int* count_pin = nullptr;     // (inside median_pin)
   // the median range runs on the S2M stream (it is read after the S2S align),
   // beside the scan's index build: med_in = the voxel output is ready, med_done
   hipEvent_t med_in = nullptr, med_done = nullptr;
@@ -497,8 +497,7 @@ struct ddlo_odom {
   double thresh_dist = 1.0;
   int64_t submap_points = 0;
   // process_dynamic: the residual image, the frame's objects and the segments to cut out
-  float* resid_pin = nullptr;   // pinned, resid_cap pixels
-  size_t resid_cap = 0;
+  PinBuf resid_pin;
   std::vector<ddlo_seg_object> dyn_objs;
   std::vector<uint8_t> dyn_flags;
   std::vector<int32_t> dyn_remove;
@@ -760,17 +759,12 @@ gicp_status dynamic_step(ddlo_odom* o, const DynStep& d, int npts, size_t stride
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(o->s));
   }
-  if (o->resid_cap < (size_t)npix) {
-    if (o->resid_pin) (void)hipHostFree(o->resid_pin);
-    o->resid_pin = nullptr;
-    o->resid_cap = 0;
-    HIP_TRY(hipHostMalloc((void**)&o->resid_pin, sizeof(float) * (size_t)npix, hipHostMallocDefault));
-    o->resid_cap = (size_t)npix;
-  }
-  st = gicp_residual_image(o->s2m, d.dp.theta_min, d.dp.theta_max, sp.cols, sp.rows, o->resid_pin, nullptr);
+  HIP_TRY(o->resid_pin.ensure(sizeof(float) * (size_t)npix));
+  float* const resid = o->resid_pin.as<float>();
+  st = gicp_residual_image(o->s2m, d.dp.theta_min, d.dp.theta_max, sp.cols, sp.rows, resid, nullptr);
   if (st) return st;
   ddlo_seg_result sr{};
-  st = seg_process_staged(d.seg, o->T, o->resid_pin, &sr);
+  st = seg_process_staged(d.seg, o->T, resid, &sr);
   if (st) return st;
   if (d.cloud) {
     st = seg_project_commit(d.seg);
@@ -927,17 +921,16 @@ gicp_status ddlo_odom_create(int device, const ddlo_odom_params* p, ddlo_odom** 
   }
   o->s = o->s2s->stream;  // one stream: the driver's work is one dependent chain
   o->timing = dev_getenv("DDLO_ODOM_TIMING") != nullptr;
-  if (hipHostMalloc((void**)&o->median_pin, sizeof(float) * 20, hipHostMallocDefault) != hipSuccess ||
+  if (o->median_pin.reset(sizeof(float) * 20) != hipSuccess ||
       hipEventCreateWithFlags(&o->med_in, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&o->med_done, hipEventDisableTiming) != hipSuccess) {
-    if (o->median_pin) (void)hipHostFree(o->median_pin);
     if (o->med_in) (void)hipEventDestroy(o->med_in);
     gicp_ctx_destroy(o->s2s);
     gicp_ctx_destroy(o->s2m);
     return fail(GICP_EHIP, "pinned allocation failed");
   }
-  *o->median_pin = 0.f;
-  o->count_pin = reinterpret_cast<int*>(o->median_pin + 4);
+  *o->median_pin.as<float>() = 0.f;
+  o->count_pin = reinterpret_cast<int*>(o->median_pin.as<float>() + 4);
   mat4_identity(o->T);
   mat4_identity(o->T_s2s);
   mat4_identity(o->T_s2s_prev);
@@ -959,8 +952,6 @@ gicp_status ddlo_odom_destroy(ddlo_odom* o) {
     std::fprintf(stderr, "\n");
   }
   o->keyframes.clear();
-  if (o->median_pin) (void)hipHostFree(o->median_pin);
-  if (o->resid_pin) (void)hipHostFree(o->resid_pin);
   if (o->med_in) (void)hipEventDestroy(o->med_in);
   if (o->med_done) (void)hipEventDestroy(o->med_done);
   gicp_ctx_destroy(o->s2m);
@@ -1039,16 +1030,16 @@ static gicp_status process_scan(ddlo_odom* o, const float* xyz, size_t n, size_t
     HIP_TRY(hipStreamWaitEvent(sm, o->med_in, 0));
     if (m > 0)
       median_range_async(sm, o->a.as<float4>(), m, o->rng.as<float>(), o->rng_sorted.as<float>(), o->medtmp.p,
-                         o->medtmp.bytes, o->median_pin);
+                         o->medtmp.bytes, o->median_pin.as<float>());
     else
-      *o->median_pin = 0.f;
+      *o->median_pin.as<float>() = 0.f;
     HIP_TRY(hipEventRecord(o->med_done, sm));
   }
   // computeMetrics + setAdaptiveParams (odom.cc:981-1001, 1156-1178), once
   // the median has arrived
   auto metrics = [&]() {
     (void)hipEventSynchronize(o->med_done);
-    const float median_curr = *o->median_pin;
+    const float median_curr = *o->median_pin.as<float>();
     if (!o->have_median) {  // static float median_prev = median_curr (first call)
       o->median_prev = median_curr;
       o->have_median = true;
@@ -1291,14 +1282,7 @@ gicp_status ddlo_odom_keyframe_points(const ddlo_odom* o, int k, float* xyz, siz
   const size_t m = std::min(cap, (size_t)kf.n);
   if (m == 0) return GICP_OK;
   HIP_TRY(hipSetDevice(o->device));
-  std::vector<float4> h(m);
-  HIP_TRY(hipMemcpy(h.data(), kf.pts.p, sizeof(float4) * m, hipMemcpyDeviceToHost));   // (idle: process waited for it)
-  for (size_t i = 0; i < m; ++i) {
-    xyz[3 * i] = h[i].x;
-    xyz[3 * i + 1] = h[i].y;
-    xyz[3 * i + 2] = h[i].z;
-  }
-  return GICP_OK;
+  return read_xyz(nullptr, kf.pts.as<float4>(), m, xyz);   // the null stream (idle: process waited for the keyframe)
 }
 
 gicp_status ddlo_odom_keyframe(const ddlo_odom* o, int k, float pose7[7], size_t* npoints) {
@@ -1352,14 +1336,7 @@ gicp_status ddlo_preprocess(int device, const float* xyz, size_t n, size_t strid
   *nout = (size_t)m;
   if (out && m > 0) {
     if ((size_t)m > cap) return fail(GICP_EINVAL, "output capacity too small");
-    std::vector<float4> h(m);
-    HIP_TRY(hipMemcpyAsync(h.data(), o->a.p, sizeof(float4) * m, hipMemcpyDeviceToHost, o->s));
-    HIP_TRY(hipStreamSynchronize(o->s));
-    for (int i = 0; i < m; ++i) {
-      out[3 * i] = h[i].x;
-      out[3 * i + 1] = h[i].y;
-      out[3 * i + 2] = h[i].z;
-    }
+    return read_xyz(o->s, o->a.as<float4>(), (size_t)m, out);
   }
   return GICP_OK;
 }
@@ -1382,10 +1359,10 @@ gicp_status ddlo_median_range(int device, const float* xyz, size_t n, size_t str
   HIP_TRY(o->rng_sorted.ensure(sizeof(float) * n));
   HIP_TRY(o->medtmp.ensure(median_tmp_bytes((int)n)));
   median_range_async(o->s, o->a.as<float4>(), (int)n, o->rng.as<float>(), o->rng_sorted.as<float>(), o->medtmp.p,
-                     o->medtmp.bytes, o->median_pin);
+                     o->medtmp.bytes, o->median_pin.as<float>());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(o->s));
-  *median = *o->median_pin;
+  *median = *o->median_pin.as<float>();
   return GICP_OK;
 }
 

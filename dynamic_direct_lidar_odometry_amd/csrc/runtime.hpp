@@ -163,6 +163,36 @@ inline PinnedPool& pinned_pool() {
   return *pool;
 }
 
+// A pinned host block owned by one handle (staging of small transfers, count
+// and record read-backs), grown on demand: its contents are dropped when it
+// grows.  Not from PinnedPool: nothing recycles or zero-fills these.
+struct PinBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  PinBuf() = default;
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf() {
+    if (p) (void)hipHostFree(p);
+  }
+  // a new block of exactly b bytes (the fixed-size blocks, or a growth rule of the caller's own)
+  hipError_t reset(size_t b) {
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    bytes = 0;
+    const hipError_t e = hipHostMalloc(&p, b, hipHostMallocDefault);
+    if (e != hipSuccess) p = nullptr;
+    else bytes = b;
+    return e;
+  }
+  // at least b bytes: twice what is asked for, so that a slowly growing need does not reallocate every time
+  hipError_t ensure(size_t b) { return b <= bytes ? hipSuccess : reset(std::max<size_t>(2 * b, 4096)); }
+  template <class T>
+  T* as() const {
+    return static_cast<T*>(p);
+  }
+};
+
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
@@ -194,6 +224,20 @@ struct DevBuf {
     return static_cast<T*>(p);
   }
 };
+
+// m float4 points of device memory as xyz triples in out: read back on the
+// stream into a pageable temporary, waited for, then unpacked
+inline gicp_status read_xyz(hipStream_t s, const float4* dev, size_t m, float* out) {
+  std::vector<float4> h(m);
+  HIP_TRY(hipMemcpyAsync(h.data(), dev, sizeof(float4) * m, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (size_t i = 0; i < m; ++i) {
+    out[3 * i] = h[i].x;
+    out[3 * i + 1] = h[i].y;
+    out[3 * i + 2] = h[i].z;
+  }
+  return GICP_OK;
+}
 
 // nanoflann's own kd-tree of a cloud (nftree.hip), built on first need: the
 // order in which the reference's search meets equidistant points.

@@ -32,7 +32,7 @@
 
 #include "../../include/ddlo_segment.h"
 #include "runtime.hpp"
-#include "seg_internal.hpp"
+#include "seg_state.hpp"
 
 namespace ddlo {
 
@@ -229,73 +229,63 @@ const ClsSelSet kCloudSels = {{{DDLO_CLS_GROUND, 0, DDLO_CLS_VALID},
 
 struct SegClasses {
   DevBuf img, table, partial, counts, pcount, poffs, totals, clouds, ids;
-  ClsTrack* pin_table = nullptr;   // pinned staging of the tracks' table
-  size_t pin_tracks = 0;
-  int* pin_back = nullptr;         // pinned: counts (8 ints), then totals (4 ints)
+  rt::PinBuf pin_table;            // pinned staging of the tracks' table
+  rt::PinBuf pin_back;             // pinned: counts (8 ints), then totals (4 ints)
   bool have_img = false;
   unsigned long long serial = 0;   // the scan the image belongs to
   bool have_clouds = false;
   int cloud_n[kClsSels] = {0, 0, 0, 0};
 
+  // room for the table of `tracks` tracks (doubled, 64 at least), and the read-back block
   gicp_status stage(size_t tracks) {
-    if (!pin_back) HIP_TRY(hipHostMalloc((void**)&pin_back, sizeof(int) * 16, hipHostMallocDefault));
-    if (tracks <= pin_tracks) return GICP_OK;
-    if (pin_table) (void)hipHostFree(pin_table);
-    pin_table = nullptr;
-    pin_tracks = 0;
-    const size_t want = std::max<size_t>(2 * tracks, 64);
-    HIP_TRY(hipHostMalloc((void**)&pin_table, sizeof(ClsTrack) * want, hipHostMallocDefault));
-    pin_tracks = want;
+    if (!pin_back.p) HIP_TRY(pin_back.reset(sizeof(int) * 16));
+    if (sizeof(ClsTrack) * tracks <= pin_table.bytes) return GICP_OK;
+    HIP_TRY(pin_table.reset(sizeof(ClsTrack) * std::max<size_t>(2 * tracks, 64)));
     return GICP_OK;
   }
 };
 
-void seg_classes_free(SegClasses* c) {
-  if (!c) return;
-  if (c->pin_table) (void)hipHostFree(c->pin_table);
-  if (c->pin_back) (void)hipHostFree(c->pin_back);
-  delete c;
-}
+void SegPartFree::operator()(SegClasses* c) const { delete c; }
 
 namespace {
 
 int workgroups(int npix) { return (npix + kClsThreads - 1) / kClsThreads; }
 
 // the class image of the last scan, or GICP_EINVAL
-gicp_status current(ddlo_seg* s, SegClassView* v, SegClasses** c) {
-  if (gicp_status st = seg_classes_view(s, v)) return st;
-  if (!v->have) return fail(GICP_EINVAL, "no processed scan");
-  *c = *v->slot;
-  if (!*c || !(*c)->have_img || (*c)->serial != v->serial)
+gicp_status current(ddlo_seg* s, SegClasses** c) {
+  if (!s->have) return fail(GICP_EINVAL, "no processed scan");
+  *c = s->classes.get();
+  if (!*c || !(*c)->have_img || (*c)->serial != s->scan_serial)
     return fail(GICP_EINVAL, "the last scan is not classified (ddlo_seg_classify)");
-  HIP_TRY(hipSetDevice(v->device));
+  HIP_TRY(hipSetDevice(s->device));
   return GICP_OK;
 }
 
 // the three-step partition over c->img; the totals reach pin_back[8 ..] with the stream's next wait
 template <bool kIds>
-gicp_status partition(const SegClassView& v, SegClasses* c, const ClsSelSet& sel) {
-  const int npix = v.rows * v.cols, nwg = workgroups(npix);
+gicp_status partition(const ddlo_seg* s, SegClasses* c, const ClsSelSet& sel) {
+  const int npix = s->p.rows * s->p.cols, nwg = workgroups(npix);
+  const hipStream_t stream = s->s;
   HIP_TRY(c->pcount.ensure(sizeof(int) * kClsSels * (size_t)nwg));
   HIP_TRY(c->poffs.ensure(sizeof(int) * kClsSels * (size_t)nwg));
   HIP_TRY(c->totals.ensure(sizeof(int) * kClsSels));
   if (kIds) HIP_TRY(c->ids.ensure(sizeof(int) * (size_t)npix * (size_t)sel.n));
   else HIP_TRY(c->clouds.ensure(sizeof(float4) * (size_t)npix * (size_t)sel.n));
-  k_cls_part_count<<<nwg, kClsThreads, 0, v.stream>>>(c->img.as<unsigned char>(), npix, sel, c->pcount.as<int>());
-  k_cls_part_scan<<<1, kClsThreads, 0, v.stream>>>(c->pcount.as<int>(), nwg, c->poffs.as<int>(), c->totals.as<int>());
-  k_cls_part_write<kIds><<<nwg, kClsThreads, 0, v.stream>>>(c->img.as<unsigned char>(), npix, sel, c->poffs.as<int>(),
-                                                           v.raw, v.stride, c->clouds.as<float4>(), c->ids.as<int>(),
-                                                           npix);
+  k_cls_part_count<<<nwg, kClsThreads, 0, stream>>>(c->img.as<unsigned char>(), npix, sel, c->pcount.as<int>());
+  k_cls_part_scan<<<1, kClsThreads, 0, stream>>>(c->pcount.as<int>(), nwg, c->poffs.as<int>(), c->totals.as<int>());
+  k_cls_part_write<kIds><<<nwg, kClsThreads, 0, stream>>>(c->img.as<unsigned char>(), npix, sel, c->poffs.as<int>(),
+                                                         s->raw.as<unsigned char>(), s->raw_stride,
+                                                         c->clouds.as<float4>(), c->ids.as<int>(), npix);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(c->pin_back + 8, c->totals.p, sizeof(int) * kClsSels, hipMemcpyDeviceToHost, v.stream));
+  HIP_TRY(hipMemcpyAsync(c->pin_back.as<int>() + 8, c->totals.p, sizeof(int) * kClsSels, hipMemcpyDeviceToHost, stream));
   return GICP_OK;
 }
 
-gicp_status ensure_clouds(const SegClassView& v, SegClasses* c) {
+gicp_status ensure_clouds(const ddlo_seg* s, SegClasses* c) {
   if (c->have_clouds) return GICP_OK;
-  if (gicp_status st = partition<false>(v, c, kCloudSels)) return st;
-  HIP_TRY(hipStreamSynchronize(v.stream));
-  for (int k = 0; k < kClsSels; ++k) c->cloud_n[k] = c->pin_back[8 + k];
+  if (gicp_status st = partition<false>(s, c, kCloudSels)) return st;
+  HIP_TRY(hipStreamSynchronize(s->s));
+  for (int k = 0; k < kClsSels; ++k) c->cloud_n[k] = c->pin_back.as<int>()[8 + k];
   c->have_clouds = true;
   return GICP_OK;
 }
@@ -304,11 +294,10 @@ gicp_status ensure_clouds(const SegClassView& v, SegClasses* c) {
 
 gicp_status seg_frame_clouds_dev(ddlo_seg* s, const float4* pts[4], int count[4]) {
   if (!s || !pts || !count) return fail(GICP_EINVAL, "null argument");
-  SegClassView v;
   SegClasses* c = nullptr;
-  if (gicp_status st = current(s, &v, &c)) return st;
-  if (gicp_status st = ensure_clouds(v, c)) return st;
-  const size_t npix = (size_t)v.rows * v.cols;
+  if (gicp_status st = current(s, &c)) return st;
+  if (gicp_status st = ensure_clouds(s, c)) return st;
+  const size_t npix = (size_t)s->p.rows * s->p.cols;
   for (int k = 0; k < kClsSels; ++k) {
     pts[k] = c->clouds.as<float4>() + npix * k;
     count[k] = c->cloud_n[k];
@@ -318,9 +307,8 @@ gicp_status seg_frame_clouds_dev(ddlo_seg* s, const float4* pts[4], int count[4]
 
 gicp_status seg_class_image_dev(ddlo_seg* s, const unsigned char** img) {
   if (!s || !img) return fail(GICP_EINVAL, "null argument");
-  SegClassView v;
   SegClasses* c = nullptr;
-  if (gicp_status st = current(s, &v, &c)) return st;
+  if (gicp_status st = current(s, &c)) return st;
   *img = c->img.as<unsigned char>();
   return GICP_OK;
 }
@@ -334,9 +322,7 @@ extern "C" {
 gicp_status ddlo_seg_classify(ddlo_seg* s, const int32_t* track_ids, const int32_t* statuses, size_t n,
                               ddlo_seg_class_counts* counts) {
   if (!s || (n && (!track_ids || !statuses))) return fail(GICP_EINVAL, "invalid argument");
-  SegClassView v;
-  if (gicp_status st = seg_classes_view(s, &v)) return st;
-  if (!v.have) return fail(GICP_EINVAL, "no processed scan");
+  if (!s->have) return fail(GICP_EINVAL, "no processed scan");
   if (n > (size_t)kClsMaxTracks) return fail(GICP_EINVAL, "too many tracks");
   for (size_t i = 0; i < n; ++i) {
     if (statuses[i] < 0 || statuses[i] > 2) return fail(GICP_EINVAL, "a status is not 0, 1 or 2");
@@ -347,10 +333,11 @@ gicp_status ddlo_seg_classify(ddlo_seg* s, const int32_t* track_ids, const int32
   const int* pool = nullptr;
   if (gicp_status st = seg_tracks_ranges(s, track_ids, n, &ranges, &pool)) return st;
   // valid: from here on the image is rewritten
-  HIP_TRY(hipSetDevice(v.device));
-  SegClasses* c = *v.slot;
-  if (!c) *v.slot = c = new SegClasses();
-  const int npix = v.rows * v.cols, npad = (npix + 3) / 4 * 4, nwg = workgroups(npix);
+  HIP_TRY(hipSetDevice(s->device));
+  if (!s->classes) s->classes.reset(new SegClasses());
+  SegClasses* const c = s->classes.get();
+  const hipStream_t stream = s->s;
+  const int npix = s->p.rows * s->p.cols, npad = (npix + 3) / 4 * 4, nwg = workgroups(npix);
   std::vector<ClsTrack> table;
   int maxlen = 0;
   for (size_t i = 0; i < n; ++i) {
@@ -362,29 +349,30 @@ gicp_status ddlo_seg_classify(ddlo_seg* s, const int32_t* track_ids, const int32
   HIP_TRY(c->img.ensure((size_t)npad));
   c->have_img = false;
   c->have_clouds = false;
-  ClsBaseArgs a{v.raw, v.stride, v.ground, npix, npad, (v.rows - v.ground_rows) * v.cols, c->img.as<unsigned char>()};
-  k_cls_base<<<(npad + kClsThreads - 1) / kClsThreads, kClsThreads, 0, v.stream>>>(a);
+  ClsBaseArgs a{s->raw.as<unsigned char>(), s->raw_stride, s->ground.as<signed char>(), npix, npad,
+                (s->p.rows - s->p.ground_rows) * s->p.cols, c->img.as<unsigned char>()};
+  k_cls_base<<<(npad + kClsThreads - 1) / kClsThreads, kClsThreads, 0, stream>>>(a);
   if (!table.empty() && pool) {
     const size_t tb = sizeof(ClsTrack) * table.size();
     HIP_TRY(c->table.ensure(tb));
-    std::memcpy(c->pin_table, table.data(), tb);
-    HIP_TRY(hipMemcpyAsync(c->table.p, c->pin_table, tb, hipMemcpyHostToDevice, v.stream));
-    k_cls_paint<<<dim3(chunks_for(maxlen), (unsigned)table.size()), kClsThreads, 0, v.stream>>>(
+    std::memcpy(c->pin_table.p, table.data(), tb);
+    HIP_TRY(hipMemcpyAsync(c->table.p, c->pin_table.p, tb, hipMemcpyHostToDevice, stream));
+    k_cls_paint<<<dim3(chunks_for(maxlen), (unsigned)table.size()), kClsThreads, 0, stream>>>(
         c->table.as<ClsTrack>(), pool, c->img.as<unsigned>(), npix);
   }
   if (counts) {
     HIP_TRY(c->partial.ensure(sizeof(int) * kClsCounts * (size_t)nwg));
     HIP_TRY(c->counts.ensure(sizeof(int) * kClsCounts));
-    k_cls_count<<<nwg, kClsThreads, 0, v.stream>>>(c->img.as<unsigned char>(), npix, c->partial.as<int>());
-    k_cls_count_sum<<<1, kClsThreads, 0, v.stream>>>(c->partial.as<int>(), nwg, c->counts.as<int>());
-    HIP_TRY(hipMemcpyAsync(c->pin_back, c->counts.p, sizeof(int) * kClsCounts, hipMemcpyDeviceToHost, v.stream));
+    k_cls_count<<<nwg, kClsThreads, 0, stream>>>(c->img.as<unsigned char>(), npix, c->partial.as<int>());
+    k_cls_count_sum<<<1, kClsThreads, 0, stream>>>(c->partial.as<int>(), nwg, c->counts.as<int>());
+    HIP_TRY(hipMemcpyAsync(c->pin_back.p, c->counts.p, sizeof(int) * kClsCounts, hipMemcpyDeviceToHost, stream));
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(v.stream));   // the staged table is free again; the image is complete
+  HIP_TRY(hipStreamSynchronize(stream));   // the staged table is free again; the image is complete
   c->have_img = true;
-  c->serial = v.serial;
+  c->serial = s->scan_serial;
   if (counts) {
-    const int* b = c->pin_back;
+    const int* b = c->pin_back.as<int>();
     *counts = ddlo_seg_class_counts{b[0], b[1], b[2], b[3], b[4], b[5], b[6], 0};
   }
   return GICP_OK;
@@ -392,58 +380,44 @@ gicp_status ddlo_seg_classify(ddlo_seg* s, const int32_t* track_ids, const int32
 
 gicp_status ddlo_seg_class_image(ddlo_seg* s, uint8_t* img) {
   if (!s || !img) return fail(GICP_EINVAL, "invalid argument");
-  SegClassView v;
   SegClasses* c = nullptr;
-  if (gicp_status st = current(s, &v, &c)) return st;
-  HIP_TRY(hipMemcpyAsync(img, c->img.p, (size_t)v.rows * v.cols, hipMemcpyDeviceToHost, v.stream));
-  HIP_TRY(hipStreamSynchronize(v.stream));
+  if (gicp_status st = current(s, &c)) return st;
+  HIP_TRY(hipMemcpyAsync(img, c->img.p, (size_t)s->p.rows * s->p.cols, hipMemcpyDeviceToHost, s->s));
+  HIP_TRY(hipStreamSynchronize(s->s));
   return GICP_OK;
 }
 
 gicp_status ddlo_seg_class_indices(ddlo_seg* s, int any, int none, int32_t* out, size_t cap, size_t* n) {
   if (!s || !n || (!out && cap)) return fail(GICP_EINVAL, "invalid argument");
   if ((any & ~0xff) || (none & ~0xff)) return fail(GICP_EINVAL, "any and none are masks over the class byte");
-  SegClassView v;
   SegClasses* c = nullptr;
-  if (gicp_status st = current(s, &v, &c)) return st;
+  if (gicp_status st = current(s, &c)) return st;
   const ClsSelSet sel = {{{(unsigned)any, (unsigned)none, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, 1};
-  if (gicp_status st = partition<true>(v, c, sel)) return st;
-  HIP_TRY(hipStreamSynchronize(v.stream));
-  const size_t m = (size_t)c->pin_back[8];
+  if (gicp_status st = partition<true>(s, c, sel)) return st;
+  HIP_TRY(hipStreamSynchronize(s->s));
+  const size_t m = (size_t)c->pin_back.as<int>()[8];
   *n = m;
   const size_t k = std::min(m, cap);
   if (!out || k == 0) return GICP_OK;
-  HIP_TRY(hipMemcpyAsync(out, c->ids.p, sizeof(int32_t) * k, hipMemcpyDeviceToHost, v.stream));
-  HIP_TRY(hipStreamSynchronize(v.stream));
+  HIP_TRY(hipMemcpyAsync(out, c->ids.p, sizeof(int32_t) * k, hipMemcpyDeviceToHost, s->s));
+  HIP_TRY(hipStreamSynchronize(s->s));
   return GICP_OK;
 }
 
 gicp_status ddlo_seg_frame_clouds(ddlo_seg* s, ddlo_seg_frame_clouds_out* out) {
   if (!s || !out) return fail(GICP_EINVAL, "invalid argument");
-  SegClassView v;
   SegClasses* c = nullptr;
-  if (gicp_status st = current(s, &v, &c)) return st;
-  if (gicp_status st = ensure_clouds(v, c)) return st;
+  if (gicp_status st = current(s, &c)) return st;
+  if (gicp_status st = ensure_clouds(s, c)) return st;
   ddlo_seg_cloud_out* const o[kClsSels] = {&out->ground, &out->non_static, &out->dynamic, &out->static_points};
   for (int k = 0; k < kClsSels; ++k) {
     o[k]->n = (size_t)c->cloud_n[k];
     if (o[k]->xyz && o[k]->cap < o[k]->n) return fail(GICP_EINVAL, "output capacity too small");
   }
-  const size_t npix = (size_t)v.rows * v.cols;
-  std::vector<float4> h;
+  const size_t npix = (size_t)s->p.rows * s->p.cols;
   for (int k = 0; k < kClsSels; ++k) {
-    const size_t m = o[k]->n;
-    if (!o[k]->xyz || m == 0) continue;
-    h.resize(m);
-    HIP_TRY(hipMemcpyAsync(h.data(), c->clouds.as<float4>() + npix * k, sizeof(float4) * m, hipMemcpyDeviceToHost,
-                           v.stream));
-    HIP_TRY(hipStreamSynchronize(v.stream));
-    float* xyz = o[k]->xyz;
-    for (size_t i = 0; i < m; ++i) {
-      xyz[3 * i] = h[i].x;
-      xyz[3 * i + 1] = h[i].y;
-      xyz[3 * i + 2] = h[i].z;
-    }
+    if (!o[k]->xyz || o[k]->n == 0) continue;
+    if (gicp_status st = rt::read_xyz(s->s, c->clouds.as<float4>() + npix * k, o[k]->n, o[k]->xyz)) return st;
   }
   return GICP_OK;
 }

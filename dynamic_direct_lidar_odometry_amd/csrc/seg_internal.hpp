@@ -1,10 +1,9 @@
 // seg_internal.hpp — the segmentation's entries for the odometry driver
 // (odom.hip, ddlo_odom_process_dynamic): the scan and the keyframe cloud stay
-// on the device between the two.
+// on the device between the two.  The handle itself is seg_state.hpp's.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <functional>
 #include <vector>
 
 #include "../../include/ddlo_segment.h"
@@ -22,34 +21,9 @@ gicp_status seg_objects_vec(ddlo_seg* s, float max_dim_ratio, std::vector<ddlo_s
 // until the next call on s) and *count; complete when the call returns.
 gicp_status seg_static_cloud_dev(ddlo_seg* s, const int32_t* remove_ids, size_t n_remove, const float centre[3],
                                  double crop_size, double leaf, const float4** pts, int* count);
-// the same with one more removal between the packing and the crop / voxel
-// pass: more(stream, packed scan, pixels) may write NaN over further points
-using SegDropHook = std::function<gicp_status(hipStream_t, float4*, int)>;
-gicp_status seg_static_cloud_with(ddlo_seg* s, const int32_t* remove_ids, size_t n_remove, const float centre[3],
-                                  double crop_size, double leaf, const float4** pts, int* count, const SegDropHook* more);
-
-// The tracks' pixel lists (seg_tracks.hip) live in the segmentation handle;
-// what they need of it: its stream and image size, and the last scan's
-// segments as CSR on the device (device labelling: the labelling's own; host
-// labelling: the upload made for k_seg_objects, made here if the objects were
-// not asked for) with every segment's length on the host.
-struct SegTracks;
-void seg_tracks_free(SegTracks* t);
-struct SegTrackView {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  int npix = 0;
-  bool have = false;           // a scan was processed
-  int segments = 0;
-  // with_csr only:
-  const int* d_off = nullptr;  // segments + 2 offsets
-  const int* d_pix = nullptr;
-  std::vector<int> len;        // [l] for l = 1 .. segments
-  SegTracks** slot = nullptr;
-};
-gicp_status seg_tracks_view(ddlo_seg* s, SegTrackView* v, bool with_csr);
-// ddlo_seg_static_cloud_tracks, the result left on the device as seg_static_cloud_dev
-// leaves it; *dropped (optional) = the sum of the removed lists' lengths
+// ddlo_seg_static_cloud_tracks (seg_tracks.hip), the result left on the device
+// as seg_static_cloud_dev leaves it; *dropped (optional) = the sum of the
+// removed lists' lengths
 gicp_status seg_static_cloud_tracks_dev(ddlo_seg* s, const int32_t* track_ids, size_t n, const float centre[3],
                                         double crop_size, double leaf, const float4** pts, int* count, int64_t* dropped);
 // the pool ranges (offset, length) of the lists of the tracks in track_ids,
@@ -58,46 +32,15 @@ gicp_status seg_static_cloud_tracks_dev(ddlo_seg* s, const int32_t* track_ids, s
 gicp_status seg_tracks_ranges(ddlo_seg* s, const int32_t* track_ids, size_t n, std::vector<int2>* ranges,
                               const int** pool);
 
-// The per-pixel classes (seg_classes.hip) live in the segmentation handle;
-// what they need of it: the scan as ddlo_seg_process saw it (never the packed
-// copy ddlo_seg_static_cloud* writes NaN over), the device ground image, and
-// a serial that changes with every scan handed in.
-struct SegClasses;
-void seg_classes_free(SegClasses* c);
-struct SegClassView {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  int rows = 0, cols = 0, ground_rows = 0;
-  bool have = false;                    // a scan was processed
-  unsigned long long serial = 0;        // of the scan in raw
-  const unsigned char* raw = nullptr;   // x, y, z floats first, stride bytes apart
-  size_t stride = 0;
-  const signed char* ground = nullptr;  // ground_mat_
-  SegClasses** slot = nullptr;
-};
-gicp_status seg_classes_view(ddlo_seg* s, SegClassView* v);
 // ddlo_seg_frame_clouds' results as they lie on the device after it (ground,
 // non-static, dynamic, static: float4, w = 0), valid until the next
 // ddlo_seg_classify on s; complete when the call returns.
 gicp_status seg_frame_clouds_dev(ddlo_seg* s, const float4* pts[4], int count[4]);
-
 // the class image of the last scan on the device (rows x cols bytes), or
 // GICP_EINVAL as ddlo_seg_class_image; no device work
 gicp_status seg_class_image_dev(ddlo_seg* s, const unsigned char** img);
 
-// The projection of an unorganized cloud (seg_project.hip): its maps and
-// scratch live in the segmentation handle; what they need of it.
-struct SegProject;
-void seg_project_free(SegProject* p);
-struct SegProjView {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  ddlo_seg_params params{};
-  bool have = false;                 // a scan was processed
-  unsigned long long serial = 0;     // of the scan in the handle
-  SegProject** slot = nullptr;
-};
-gicp_status seg_project_view(ddlo_seg* s, SegProjView* v);
+// The projection of an unorganized cloud (seg_project.hip).
 // proj (NULL: the defaults of s) checked and resolved into *out; no device work
 gicp_status seg_projection_resolve(ddlo_seg* s, const ddlo_seg_projection* proj, ddlo_seg_projection* out);
 // Claim and fill: the n points in raw (device memory, stride bytes apart,

@@ -31,7 +31,7 @@
 
 #include "../../include/ddlo_segment.h"
 #include "runtime.hpp"
-#include "seg_internal.hpp"
+#include "seg_state.hpp"
 
 namespace ddlo {
 
@@ -183,37 +183,33 @@ struct SegProject {
   DevBuf partial;   // [2 * claim workgroups][fill workgroups]
   DevBuf counts;    // [4]
   DevBuf pcls;      // [n] ddlo_seg_point_classes' result
-  int* pin = nullptr;   // pinned: the counts' read-back
+  rt::PinBuf pin;       // pinned: the counts' read-back (4 ints)
   int n = 0;            // points of the last projection
   bool staged = false;  // seg_project_dev ran; seg_project_commit has not
   bool have = false;    // the maps are those of scan `serial`
   unsigned long long serial = 0;
 };
 
-void seg_project_free(SegProject* p) {
-  if (!p) return;
-  if (p->pin) (void)hipHostFree(p->pin);
-  delete p;
-}
+void SegPartFree::operator()(SegProject* p) const { delete p; }
 
 namespace {
 
-gicp_status project_of(const SegProjView& v, SegProject** out) {
-  SegProject* p = *v.slot;
-  if (!p) *v.slot = p = new SegProject();
-  if (!p->pin) HIP_TRY(hipHostMalloc((void**)&p->pin, sizeof(int) * 4, hipHostMallocDefault));
+// the part, made on first use (the device is set)
+gicp_status project_of(ddlo_seg* s, SegProject** out) {
+  if (!s->project) s->project.reset(new SegProject());
+  SegProject* const p = s->project.get();
+  if (!p->pin.p) HIP_TRY(p->pin.reset(sizeof(int) * 4));
   *out = p;
   return GICP_OK;
 }
 
 // the maps of the handle's scan, or GICP_EINVAL
-gicp_status current(ddlo_seg* s, SegProjView* v, SegProject** p) {
-  if (gicp_status st = seg_project_view(s, v)) return st;
-  *p = *v->slot;
+gicp_status current(ddlo_seg* s, SegProject** p) {
+  *p = s->project.get();
   if (!*p || !(*p)->have) return fail(GICP_EINVAL, "no projected scan (ddlo_seg_process_cloud)");
-  if (!v->have || (*p)->serial != v->serial)
+  if (!s->have || (*p)->serial != s->scan_serial)
     return fail(GICP_EINVAL, "the last scan was organized: the projection maps belong to an earlier scan");
-  HIP_TRY(hipSetDevice(v->device));
+  HIP_TRY(hipSetDevice(s->device));
   return GICP_OK;
 }
 
@@ -241,9 +237,7 @@ gicp_status seg_projection_resolve(ddlo_seg* s, const ddlo_seg_projection* proj,
   if (proj) {
     *out = *proj;
   } else {
-    ddlo_seg_params sp;
-    if (gicp_status st = seg_get_params(s, &sp)) return st;
-    if (gicp_status st = default_projection(sp, out)) return st;
+    if (gicp_status st = default_projection(s->p, out)) return st;
   }
   return check_projection(*out);
 }
@@ -252,11 +246,9 @@ gicp_status seg_project_dev(ddlo_seg* s, hipStream_t st, const unsigned char* ra
                             const ddlo_seg_projection& proj, ddlo_seg_projection_result* out) {
   if (!s || !T || (!raw && n) || n < 0) return fail(GICP_EINVAL, "invalid argument");
   if (gicp_status e = check_projection(proj)) return e;
-  SegProjView v;
-  if (gicp_status e = seg_project_view(s, &v)) return e;
-  HIP_TRY(hipSetDevice(v.device));
+  HIP_TRY(hipSetDevice(s->device));
   SegProject* p = nullptr;
-  if (gicp_status e = project_of(v, &p)) return e;
+  if (gicp_status e = project_of(s, &p)) return e;
   // valid: from here on the maps and the staged input are rewritten
   p->have = false;
   p->staged = false;
@@ -273,9 +265,9 @@ gicp_status seg_project_dev(ddlo_seg* s, hipStream_t st, const unsigned char* ra
   m.elev_res = (double)proj.elev_res_deg;
   m.azim0 = (double)proj.azim0_deg;
   m.azim_sign = (double)proj.azim_sign;
-  m.col_width = 360.0 / v.params.cols;
-  m.rows = v.params.rows;
-  m.cols = v.params.cols;
+  m.col_width = 360.0 / s->p.cols;
+  m.rows = s->p.rows;
+  m.cols = s->p.cols;
   ProjPose P;
   for (int e = 0; e < 12; ++e) P.m[e] = T[e];
   int* claim_part = p->partial.as<int>();
@@ -287,27 +279,27 @@ gicp_status seg_project_dev(ddlo_seg* s, hipStream_t st, const unsigned char* ra
   k_proj_fill<<<nwg_f, kProjThreads, 0, st>>>(p->winner.as<int>(), npix, raw, stride, n, P, buf, fill_part);
   k_proj_sum<<<1, kProjThreads, 0, st>>>(claim_part, nwg_c, fill_part, nwg_f, p->counts.as<int>());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(p->pin, p->counts.p, sizeof(int) * 3, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(p->pin.p, p->counts.p, sizeof(int) * 3, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   p->n = n;
   p->staged = true;
   if (out) {
+    const int* c = p->pin.as<int>();
     out->points = n;
-    out->invalid = p->pin[0];
-    out->out_of_view = p->pin[1];
-    out->occupied_pixels = p->pin[2];
-    out->collisions = n - p->pin[0] - p->pin[1] - p->pin[2];
+    out->invalid = c[0];
+    out->out_of_view = c[1];
+    out->occupied_pixels = c[2];
+    out->collisions = n - c[0] - c[1] - c[2];
   }
   return GICP_OK;
 }
 
 gicp_status seg_project_commit(ddlo_seg* s) {
-  SegProjView v;
-  if (gicp_status st = seg_project_view(s, &v)) return st;
-  SegProject* p = *v.slot;
-  if (!p || !p->staged || !v.have) return fail(GICP_ESTATE, "no projected scan was staged");
+  if (!s) return fail(GICP_EINVAL, "null argument");
+  SegProject* const p = s->project.get();
+  if (!p || !p->staged || !s->have) return fail(GICP_ESTATE, "no projected scan was staged");
   p->staged = false;
-  p->serial = v.serial;
+  p->serial = s->scan_serial;
   p->have = true;
   return GICP_OK;
 }
@@ -330,18 +322,16 @@ gicp_status ddlo_seg_process_cloud(ddlo_seg* s, const float* xyz, size_t n, size
   if (n > (size_t)INT32_MAX / 2) return fail(GICP_EINVAL, "cloud too large");
   ddlo_seg_projection q;
   if (gicp_status st = seg_projection_resolve(s, proj, &q)) return st;
-  SegProjView v;
-  if (gicp_status st = seg_project_view(s, &v)) return st;
-  HIP_TRY(hipSetDevice(v.device));
+  HIP_TRY(hipSetDevice(s->device));
   SegProject* p = nullptr;
-  if (gicp_status st = project_of(v, &p)) return st;
+  if (gicp_status st = project_of(s, &p)) return st;
   if (n) {
     const size_t raw_sz = (n - 1) * stride + 12;
     HIP_TRY(reserve(p->up, raw_sz));
-    HIP_TRY(hipMemcpyAsync(p->up.p, xyz, raw_sz, hipMemcpyHostToDevice, v.stream));
+    HIP_TRY(hipMemcpyAsync(p->up.p, xyz, raw_sz, hipMemcpyHostToDevice, s->s));
   }
   ddlo_seg_projection_result pr{};
-  if (gicp_status st = seg_project_dev(s, v.stream, n ? p->up.as<unsigned char>() : nullptr, stride, (int)n, T, q, &pr))
+  if (gicp_status st = seg_project_dev(s, s->s, n ? p->up.as<unsigned char>() : nullptr, stride, (int)n, T, q, &pr))
     return st;
   if (gicp_status st = seg_process_staged(s, T, residual, res)) return st;
   if (gicp_status st = seg_project_commit(s)) return st;
@@ -351,35 +341,32 @@ gicp_status ddlo_seg_process_cloud(ddlo_seg* s, const float* xyz, size_t n, size
 
 gicp_status ddlo_seg_projection_maps(ddlo_seg* s, int32_t* winner, int32_t* pixel_of_point, size_t cap, size_t* n) {
   if (!s || !n || (!pixel_of_point && cap)) return fail(GICP_EINVAL, "invalid argument");
-  SegProjView v;
   SegProject* p = nullptr;
-  if (gicp_status st = current(s, &v, &p)) return st;
+  if (gicp_status st = current(s, &p)) return st;
   *n = (size_t)p->n;
-  const size_t npix = (size_t)v.params.rows * v.params.cols, k = std::min(cap, (size_t)p->n);
-  if (winner) HIP_TRY(hipMemcpyAsync(winner, p->winner.p, sizeof(int32_t) * npix, hipMemcpyDeviceToHost, v.stream));
+  const size_t npix = (size_t)s->p.rows * s->p.cols, k = std::min(cap, (size_t)p->n);
+  if (winner) HIP_TRY(hipMemcpyAsync(winner, p->winner.p, sizeof(int32_t) * npix, hipMemcpyDeviceToHost, s->s));
   if (pixel_of_point && k)
-    HIP_TRY(hipMemcpyAsync(pixel_of_point, p->pix.p, sizeof(int32_t) * k, hipMemcpyDeviceToHost, v.stream));
-  HIP_TRY(hipStreamSynchronize(v.stream));
+    HIP_TRY(hipMemcpyAsync(pixel_of_point, p->pix.p, sizeof(int32_t) * k, hipMemcpyDeviceToHost, s->s));
+  HIP_TRY(hipStreamSynchronize(s->s));
   return GICP_OK;
 }
 
 gicp_status ddlo_seg_point_classes(ddlo_seg* s, uint8_t* out, size_t cap, size_t* n) {
   if (!s || !n || (!out && cap)) return fail(GICP_EINVAL, "invalid argument");
-  SegProjView v;
   SegProject* p = nullptr;
-  if (gicp_status st = current(s, &v, &p)) return st;
+  if (gicp_status st = current(s, &p)) return st;
   const unsigned char* img = nullptr;
   if (gicp_status st = seg_class_image_dev(s, &img)) return st;
   *n = (size_t)p->n;
   const size_t k = std::min(cap, (size_t)p->n);
   if (!out || k == 0) return GICP_OK;
   HIP_TRY(reserve(p->pcls, (size_t)p->n));
-  k_proj_point_classes<<<workgroups(p->n), kProjThreads, 0, v.stream>>>(p->pix.as<int>(), p->n, img,
-                                                                         v.params.rows * v.params.cols,
-                                                                         p->pcls.as<unsigned char>());
+  k_proj_point_classes<<<workgroups(p->n), kProjThreads, 0, s->s>>>(p->pix.as<int>(), p->n, img, s->p.rows * s->p.cols,
+                                                                     p->pcls.as<unsigned char>());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, p->pcls.p, k, hipMemcpyDeviceToHost, v.stream));
-  HIP_TRY(hipStreamSynchronize(v.stream));
+  HIP_TRY(hipMemcpyAsync(out, p->pcls.p, k, hipMemcpyDeviceToHost, s->s));
+  HIP_TRY(hipStreamSynchronize(s->s));
   return GICP_OK;
 }
 

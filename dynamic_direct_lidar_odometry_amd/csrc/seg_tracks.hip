@@ -28,7 +28,7 @@
 
 #include "../../include/ddlo_segment.h"
 #include "runtime.hpp"
-#include "seg_internal.hpp"
+#include "seg_state.hpp"
 
 namespace ddlo {
 
@@ -96,19 +96,8 @@ struct SegTracks {
   size_t used = 0;
   std::vector<Live> live;   // in pool order
   DevBuf dtable;
-  void* pin = nullptr;      // pinned staging of the table / the ranges
-  size_t pin_bytes = 0;
+  rt::PinBuf stage;         // pinned staging of the table / the ranges
 
-  gicp_status stage(size_t b) {
-    if (b <= pin_bytes) return GICP_OK;
-    if (pin) (void)hipHostFree(pin);
-    pin = nullptr;
-    pin_bytes = 0;
-    const size_t want = std::max<size_t>(2 * b, 4096);
-    HIP_TRY(hipHostMalloc(&pin, want, hipHostMallocDefault));
-    pin_bytes = want;
-    return GICP_OK;
-  }
   const Live* find(int id) const {
     for (const Live& l : live)
       if (l.id == id) return &l;
@@ -116,36 +105,34 @@ struct SegTracks {
   }
 };
 
-void seg_tracks_free(SegTracks* t) {
-  if (!t) return;
-  if (t->pin) (void)hipHostFree(t->pin);
-  delete t;
-}
+void SegPartFree::operator()(SegTracks* t) const { delete t; }
 
 namespace {
+
+const Live* find_list(const ddlo_seg* s, int id) { return s->tracks ? s->tracks->find(id) : nullptr; }
 
 gicp_status tracks_sync(ddlo_seg* s, const int32_t* track_ids, const int32_t* seg_ids, size_t n_set,
                         const int32_t* dead_ids, size_t n_dead) {
   if (!s || (n_set && (!track_ids || !seg_ids)) || (n_dead && !dead_ids)) return fail(GICP_EINVAL, "invalid argument");
-  SegTrackView v;   // without the CSR first: an invalid call does no device work
-  if (gicp_status st = seg_tracks_view(s, &v, false)) return st;
-  if (n_set && !v.have) return fail(GICP_EINVAL, "no processed scan");
-  SegTracks* t = *v.slot;
+  if (n_set && !s->have) return fail(GICP_EINVAL, "no processed scan");
+  const int segments = s->have ? s->last.segments : 0;
   for (size_t i = 0; i < n_set; ++i) {
-    if (seg_ids[i] < 1 || seg_ids[i] > v.segments) return fail(GICP_EINVAL, "seg_ids names no segment of the last scan");
+    if (seg_ids[i] < 1 || seg_ids[i] > segments) return fail(GICP_EINVAL, "seg_ids names no segment of the last scan");
     for (size_t j = 0; j < i; ++j)
       if (track_ids[j] == track_ids[i]) return fail(GICP_EINVAL, "a track id is set twice");
   }
   for (size_t i = 0; i < n_dead; ++i) {
-    if (!t || !t->find(dead_ids[i])) return fail(GICP_EINVAL, "a dead track holds no list");
+    if (!find_list(s, dead_ids[i])) return fail(GICP_EINVAL, "a dead track holds no list");
     for (size_t j = 0; j < i; ++j)
       if (dead_ids[j] == dead_ids[i]) return fail(GICP_EINVAL, "a dead track is named twice");
   }
   if (n_set == 0 && n_dead == 0) return GICP_OK;   // nothing moves: no launch
+  SegCsr csr;   // (only now: an invalid call does no device work)
   if (n_set)
-    if (gicp_status st = seg_tracks_view(s, &v, true)) return st;
-  HIP_TRY(hipSetDevice(v.device));
-  if (!t) *v.slot = t = new SegTracks();
+    if (gicp_status st = seg_csr(s, &csr)) return st;
+  HIP_TRY(hipSetDevice(s->device));
+  if (!s->tracks) s->tracks.reset(new SegTracks());
+  SegTracks* const t = s->tracks.get();
   // the next pool: the survivors in their order, then the lists set now
   std::vector<Live> next;
   std::vector<TrkEntry> table;
@@ -163,7 +150,7 @@ gicp_status tracks_sync(ddlo_seg* s, const int32_t* track_ids, const int32_t* se
     for (size_t i = 0; i < n_set && !gone; ++i) gone = track_ids[i] == l.id;
     if (!gone) add(l.id, l.off, l.len);
   }
-  for (size_t i = 0; i < n_set; ++i) add(track_ids[i], -seg_ids[i], v.len[(size_t)seg_ids[i]]);
+  for (size_t i = 0; i < n_set; ++i) add(track_ids[i], -seg_ids[i], csr.len[seg_ids[i]]);
   if (total > (size_t)INT32_MAX / 2 || table.size() > (size_t)kTrkMaxEntries)
     return fail(GICP_EINVAL, "too many track indices");
   const int nxt = t->cur ^ 1;
@@ -175,14 +162,14 @@ gicp_status tracks_sync(ddlo_seg* s, const int32_t* track_ids, const int32_t* se
   }
   if (!table.empty() && total > 0) {
     const size_t tb = sizeof(TrkEntry) * table.size();
-    if (gicp_status st = t->stage(tb)) return st;
+    HIP_TRY(t->stage.ensure(tb));
     HIP_TRY(t->dtable.ensure(tb));
-    std::memcpy(t->pin, table.data(), tb);
-    HIP_TRY(hipMemcpyAsync(t->dtable.p, t->pin, tb, hipMemcpyHostToDevice, v.stream));
-    k_trk_gather<<<dim3(chunks_for(maxlen), (unsigned)table.size()), kTrkThreads, 0, v.stream>>>(
-        t->dtable.as<TrkEntry>(), t->pool[t->cur].as<int>(), v.d_off, v.d_pix, t->pool[nxt].as<int>());
+    std::memcpy(t->stage.p, table.data(), tb);
+    HIP_TRY(hipMemcpyAsync(t->dtable.p, t->stage.p, tb, hipMemcpyHostToDevice, s->s));
+    k_trk_gather<<<dim3(chunks_for(maxlen), (unsigned)table.size()), kTrkThreads, 0, s->s>>>(
+        t->dtable.as<TrkEntry>(), t->pool[t->cur].as<int>(), csr.d_off, csr.d_pix, t->pool[nxt].as<int>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(v.stream));   // the staging and the old pool are free again
+    HIP_TRY(hipStreamSynchronize(s->s));   // the stagings and the old pool are free again
   }
   t->cur = nxt;
   t->used = total;
@@ -195,31 +182,26 @@ gicp_status tracks_sync(ddlo_seg* s, const int32_t* track_ids, const int32_t* se
 gicp_status seg_tracks_ranges(ddlo_seg* s, const int32_t* track_ids, size_t n, std::vector<int2>* ranges,
                               const int** pool) {
   if (!s || !ranges || !pool || (n && !track_ids)) return fail(GICP_EINVAL, "invalid argument");
-  SegTrackView v;
-  if (gicp_status st = seg_tracks_view(s, &v, false)) return st;
-  const SegTracks* t = *v.slot;
   ranges->clear();
   for (size_t i = 0; i < n; ++i) {
-    const Live* l = t ? t->find(track_ids[i]) : nullptr;
+    const Live* l = find_list(s, track_ids[i]);
     if (!l) return fail(GICP_EINVAL, "a track to classify holds no list");
     ranges->push_back(make_int2(l->off, l->len));
   }
-  *pool = t ? t->pool[t->cur].as<int>() : nullptr;
+  *pool = s->tracks ? s->tracks->pool[s->tracks->cur].as<int>() : nullptr;
   return GICP_OK;
 }
 
+// the removal by track list: NaN over every pixel the removed tracks list
 gicp_status seg_static_cloud_tracks_dev(ddlo_seg* s, const int32_t* track_ids, size_t n, const float centre[3],
                                         double crop_size, double leaf, const float4** pts, int* count,
                                         int64_t* dropped) {
   if (!s || (n && !track_ids)) return fail(GICP_EINVAL, "invalid argument");
-  SegTrackView v;
-  if (gicp_status st = seg_tracks_view(s, &v, false)) return st;
-  SegTracks* t = *v.slot;
   std::vector<int2> ranges;
   int maxlen = 0;
   int64_t sum = 0;
   for (size_t i = 0; i < n; ++i) {
-    const Live* l = t ? t->find(track_ids[i]) : nullptr;
+    const Live* l = find_list(s, track_ids[i]);
     if (!l) return fail(GICP_EINVAL, "a track to remove holds no list");
     if (l->len > 0) ranges.push_back(make_int2(l->off, l->len));
     maxlen = std::max(maxlen, l->len);
@@ -227,19 +209,19 @@ gicp_status seg_static_cloud_tracks_dev(ddlo_seg* s, const int32_t* track_ids, s
   }
   if (ranges.size() > (size_t)kTrkMaxEntries) return fail(GICP_EINVAL, "too many tracks to remove");
   if (dropped) *dropped = sum;
-  SegDropHook hook = [&](hipStream_t st, float4* f4, int npix) -> gicp_status {
-    if (ranges.empty()) return GICP_OK;
+  if (gicp_status st = seg_static_begin(s, centre, pts, count)) return st;
+  if (!ranges.empty()) {
+    SegTracks* const t = s->tracks.get();   // (a list was found: the part exists)
     const size_t rb = sizeof(int2) * ranges.size();
-    if (gicp_status e = t->stage(rb)) return e;
+    HIP_TRY(t->stage.ensure(rb));
     HIP_TRY(t->dtable.ensure(rb));
-    std::memcpy(t->pin, ranges.data(), rb);
-    HIP_TRY(hipMemcpyAsync(t->dtable.p, t->pin, rb, hipMemcpyHostToDevice, st));
-    k_trk_drop<<<dim3(chunks_for(maxlen), (unsigned)ranges.size()), kTrkThreads, 0, st>>>(
-        t->dtable.as<int2>(), t->pool[t->cur].as<int>(), f4, npix);
+    std::memcpy(t->stage.p, ranges.data(), rb);
+    HIP_TRY(hipMemcpyAsync(t->dtable.p, t->stage.p, rb, hipMemcpyHostToDevice, s->s));
+    k_trk_drop<<<dim3(chunks_for(maxlen), (unsigned)ranges.size()), kTrkThreads, 0, s->s>>>(
+        t->dtable.as<int2>(), t->pool[t->cur].as<int>(), s->f4.as<float4>(), (int)s->hn);
     HIP_TRY(hipGetLastError());
-    return GICP_OK;   // (seg_static_cloud_with waits for the stream before it returns)
-  };
-  return seg_static_cloud_with(s, nullptr, 0, centre, crop_size, leaf, pts, count, &hook);
+  }
+  return seg_static_finish(s, centre, crop_size, leaf, pts, count);   // (waits for the stream)
 }
 
 }  // namespace ddlo
@@ -263,33 +245,20 @@ gicp_status ddlo_seg_static_cloud_tracks(ddlo_seg* s, const int32_t* track_ids, 
   *nout = (size_t)m;
   if (!out || m == 0) return GICP_OK;
   if ((size_t)m > cap) return fail(GICP_EINVAL, "output capacity too small");
-  SegTrackView v;
-  if ((st = seg_tracks_view(s, &v, false))) return st;
-  std::vector<float4> h((size_t)m);
-  HIP_TRY(hipMemcpyAsync(h.data(), pts, sizeof(float4) * (size_t)m, hipMemcpyDeviceToHost, v.stream));
-  HIP_TRY(hipStreamSynchronize(v.stream));
-  for (int i = 0; i < m; ++i) {
-    out[3 * i] = h[i].x;
-    out[3 * i + 1] = h[i].y;
-    out[3 * i + 2] = h[i].z;
-  }
-  return GICP_OK;
+  return rt::read_xyz(s->s, pts, (size_t)m, out);
 }
 
 gicp_status ddlo_seg_track_indices(ddlo_seg* s, int32_t track_id, int32_t* out, size_t cap, size_t* n) {
   if (!s || !n || (!out && cap)) return fail(GICP_EINVAL, "invalid argument");
-  SegTrackView v;
-  if (gicp_status st = seg_tracks_view(s, &v, false)) return st;
-  const SegTracks* t = *v.slot;
-  const Live* l = t ? t->find(track_id) : nullptr;
+  const Live* l = find_list(s, track_id);
   if (!l) return fail(GICP_EINVAL, "the track holds no list");
   *n = (size_t)l->len;
   if (!out || l->len == 0) return GICP_OK;
-  HIP_TRY(hipSetDevice(v.device));
+  HIP_TRY(hipSetDevice(s->device));
   std::vector<int32_t> h((size_t)l->len);
-  HIP_TRY(hipMemcpyAsync(h.data(), t->pool[t->cur].as<int>() + l->off, sizeof(int) * h.size(), hipMemcpyDeviceToHost,
-                         v.stream));
-  HIP_TRY(hipStreamSynchronize(v.stream));
+  HIP_TRY(hipMemcpyAsync(h.data(), s->tracks->pool[s->tracks->cur].as<int>() + l->off, sizeof(int) * h.size(),
+                         hipMemcpyDeviceToHost, s->s));
+  HIP_TRY(hipStreamSynchronize(s->s));
   // ddlo_seg_label_indices' order is ascending row-major index; the host
   // labelling's lists reach the device in its push order
   std::sort(h.begin(), h.end());
@@ -299,9 +268,7 @@ gicp_status ddlo_seg_track_indices(ddlo_seg* s, int32_t track_id, int32_t* out, 
 
 gicp_status ddlo_seg_tracks_stats(const ddlo_seg* s, int32_t* lists, int64_t* indices, int64_t* capacity) {
   if (!s) return fail(GICP_EINVAL, "null handle");
-  SegTrackView v;
-  if (gicp_status st = seg_tracks_view(const_cast<ddlo_seg*>(s), &v, false)) return st;
-  const SegTracks* t = *v.slot;
+  const SegTracks* t = s->tracks.get();
   if (lists) *lists = t ? (int32_t)t->live.size() : 0;
   if (indices) *indices = t ? (int64_t)t->used : 0;
   if (capacity) *capacity = t ? (int64_t)t->cap[t->cur] : 0;

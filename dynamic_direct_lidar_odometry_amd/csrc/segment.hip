@@ -45,6 +45,7 @@
 #include "runtime.hpp"
 #include "seg_internal.hpp"
 #include "seg_label.hpp"
+#include "seg_state.hpp"
 
 namespace ddlo {
 namespace {
@@ -131,16 +132,6 @@ __global__ __launch_bounds__(256) void k_seg_pixels(SegPixelArgs a) {
 }
 
 inline int cdiv_s(long a, long b) { return (int)((a + b - 1) / b); }
-
-// The labelling's queues, kept across scans (a ddlo_seg keeps one): a fresh
-// set per scan cost four zero-filled allocations of the image size.
-struct LabelWork {
-  std::vector<int> qy, qx, py, px, rows_hit;
-  std::vector<char> line_flag;   // all zero between components
-  // the feasible segments' pixels in the order the labelling pushed them, as CSR:
-  // seg_pix[seg_off[l] .. seg_off[l + 1]) for l = 1 .. segments (seg_off[0] = seg_off[1] = 0)
-  std::vector<int> seg_off, seg_pix;
-};
 
 // cloudSegmentation + labelComponents (detection.cpp:510-724) over host images.
 struct Labeller {
@@ -463,84 +454,57 @@ void filter_objects(const std::vector<ddlo_seg_object>& recs, const double* avg,
   }
 }
 
-// pinned staging of the object kernel's small transfers (the segments' rows
-// in, the records out), grown on demand: pageable copies of a few hundred
-// bytes each cost more than the kernel
-struct ObjStage {
-  void* p = nullptr;
-  size_t bytes = 0;
-  gicp_status ensure(size_t b) {
-    if (b <= bytes) return GICP_OK;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    bytes = 0;
-    const size_t want = std::max<size_t>(2 * b, 4096);
-    HIP_TRY(hipHostMalloc(&p, want, hipHostMallocDefault));
-    bytes = want;
-    return GICP_OK;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-};
-
-void launch_objects(hipStream_t s, const unsigned char* raw, size_t stride, const int* off, const int* pix, int L,
-                    DevBuf& dobj) {
-  SegObjArgs a{raw, stride, off, pix, dobj.as<ddlo_seg_object>()};
-  k_seg_objects<<<L, kObjThreads, 0, s>>>(a);
+// the segments' rows for k_seg_objects and k_trk_gather: the L + 2 offsets,
+// then the pixel lists (CSR, as ddlo_seg_label_indices), joined in rows
+// (staging of the caller's, off[L + 1] + L + 2 ints) and sent up in one copy
+gicp_status upload_csr(hipStream_t s, const std::vector<int>& off, const std::vector<int>& pix, int L, DevBuf& dcsr,
+                       int* rows) {
+  const size_t noff = (size_t)L + 2, npix = (size_t)off[L + 1];
+  HIP_TRY(dcsr.ensure(sizeof(int) * (noff + npix)));
+  std::memcpy(rows, off.data(), sizeof(int) * noff);
+  if (npix) std::memcpy(rows + noff, pix.data(), sizeof(int) * npix);
+  HIP_TRY(hipMemcpyAsync(dcsr.p, rows, sizeof(int) * (noff + npix), hipMemcpyHostToDevice, s));
+  return GICP_OK;
 }
 
-// the same over a CSR that is on the device already (the device labelling's)
-gicp_status run_objects_dev(hipStream_t s, const unsigned char* raw, size_t stride, const int* off, const int* pix,
-                            int L, DevBuf& dobj, std::vector<ddlo_seg_object>& recs, ObjStage& stage) {
-  recs.assign((size_t)L, ddlo_seg_object{});
-  if (L <= 0) return GICP_OK;
+// where the records of L segments come back to in the pinned block that staged their rows
+size_t rec_offset(const std::vector<int>& off, int L) {
+  return (sizeof(int) * ((size_t)L + 2 + (size_t)off[L + 1]) + 63) / 64 * 64;
+}
+
+// launch the object kernel for labels 1 .. L over a CSR on the device and read
+// the records back: through rec_pin (pinned, L records), or with a pageable
+// copy when it is nullptr
+gicp_status run_objects(hipStream_t s, const unsigned char* raw, size_t stride, const int* off, const int* pix, int L,
+                        DevBuf& dobj, std::vector<ddlo_seg_object>& recs, void* rec_pin) {
   const size_t rec_b = sizeof(ddlo_seg_object) * (size_t)L;
   HIP_TRY(dobj.ensure(rec_b));
-  if (gicp_status st = stage.ensure(rec_b)) return st;
-  launch_objects(s, raw, stride, off, pix, L, dobj);
+  SegObjArgs a{raw, stride, off, pix, dobj.as<ddlo_seg_object>()};
+  k_seg_objects<<<L, kObjThreads, 0, s>>>(a);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(stage.p, dobj.p, rec_b, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(rec_pin ? rec_pin : recs.data(), dobj.p, rec_b, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  std::memcpy(recs.data(), stage.p, rec_b);
+  if (rec_pin) std::memcpy(recs.data(), rec_pin, rec_b);
   return GICP_OK;
 }
 
-// launch the object kernel for labels 1 .. L and read the records back
-// (stage: pinned staging, or nullptr for pageable copies)
-// off: L + 2 offsets, pix: off[L + 1] pixel indices (CSR, as ddlo_seg_label_indices)
-gicp_status run_objects(hipStream_t s, const unsigned char* raw, size_t stride, const std::vector<int>& off,
-                        const std::vector<int>& pix, int L, DevBuf& dcsr, DevBuf& dobj,
-                        std::vector<ddlo_seg_object>& recs, ObjStage* stage) {
-  recs.assign((size_t)L, ddlo_seg_object{});
-  if (L <= 0) return GICP_OK;
-  const size_t noff = (size_t)L + 2, npix = (size_t)off[L + 1];
-  const size_t rows_b = sizeof(int) * (noff + npix), rec_b = sizeof(ddlo_seg_object) * (size_t)L;
-  const size_t rec_off = (rows_b + 63) / 64 * 64;
-  HIP_TRY(dcsr.ensure(rows_b));
-  HIP_TRY(dobj.ensure(rec_b));
-  std::vector<int> joined;   // offsets, then the pixel lists: one upload
-  int* rows_src = nullptr;
-  void* rec_dst = recs.data();
-  if (stage) {
-    if (gicp_status st = stage->ensure(rec_off + rec_b)) return st;
-    rows_src = static_cast<int*>(stage->p);
-    rec_dst = static_cast<char*>(stage->p) + rec_off;
-  } else {
-    joined.resize(noff + npix);
-    rows_src = joined.data();
+// every label's pixels, row-major within a label (:527-537), as CSR: a
+// counting sort of the label image (labels 1 .. L), in its two passes: the
+// L + 2 offsets, then the off[L + 1] pixels
+void label_csr_offsets(const int32_t* label, size_t n, int L, std::vector<int32_t>& off) {
+  off.assign((size_t)L + 2, 0);
+  for (size_t i = 0; i < n; ++i) {
+    const int l = label[i];
+    if (l > 0 && l != kRejected) ++off[l + 1];
   }
-  std::memcpy(rows_src, off.data(), sizeof(int) * noff);
-  if (npix) std::memcpy(rows_src + noff, pix.data(), sizeof(int) * npix);
-  HIP_TRY(hipMemcpyAsync(dcsr.p, rows_src, rows_b, hipMemcpyHostToDevice, s));
-  launch_objects(s, raw, stride, dcsr.as<int>(), dcsr.as<int>() + noff, L, dobj);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(rec_dst, dobj.p, rec_b, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (stage) std::memcpy(recs.data(), rec_dst, rec_b);
-  return GICP_OK;
+  for (int l = 1; l <= L + 1; ++l) off[l] += off[l - 1];
+}
+void label_csr_pixels(const int32_t* label, size_t n, const std::vector<int32_t>& off, int32_t* pix) {
+  std::vector<int32_t> at(off.begin(), off.end() - 1);
+  for (size_t i = 0; i < n; ++i) {
+    const int l = label[i];
+    if (l > 0 && l != kRejected) pix[at[l]++] = (int32_t)i;
+  }
 }
 
 }  // namespace
@@ -551,59 +515,13 @@ gicp_status seg_check_params(const ddlo_seg_params* p) { return check_params(p);
 
 using namespace ddlo;
 
-struct ddlo_seg {
-  int device = 0;
-  ddlo_seg_params p{};
-  hipStream_t s = nullptr;
-  rt::DevBuf raw, range, ground, label;
-  size_t raw_stride = 0;              // of the scan in raw
-  // objects and the static cloud: the segments' pixel lists and the object
-  // records on the device; the packed scan, the removed pixels and the filter scratch
-  rt::DevBuf zimg, dcsr, dobj, ddrop, f4, f4b, keep, pos, vscratch, cubtmp;
-  bool have_objects = false;
-  std::vector<ddlo_seg_object> objects;   // every segment's record of the last scan (before the ratio test)
-  int* cnt_pin = nullptr;             // pinned: the filters' count read-back
-  ObjStage obj_stage;                 // pinned: the object kernel's pixel lists in, records out
-  ObjStage drop_stage;                // pinned: the removed segments' pixels
-  float* pin = nullptr;               // range | label | z (staged scans) | ground, pinned
-  size_t pin_bytes = 0;
-  std::vector<float> z;
-  // the last scan's images: the pinned read-back buffers themselves (the
-  // labelling rewrites h_label in place)
-  const float* h_range = nullptr;
-  const signed char* h_ground = nullptr;
-  int* h_label = nullptr;
-  size_t hn = 0;
-  std::vector<double> avg;
-  LabelWork work;
-  bool have = false;
-  ddlo_seg_result last{};
-  // device labelling (ddlo_seg_set_labelling): its scratch and results, the
-  // residual image on the device, the pinned record read back per frame, and
-  // which host images (kImg*) the getters have fetched for the last scan
-  int labelling = DDLO_SEG_LABEL_HOST;
-  LabelDev ldev;
-  rt::DevBuf dresid, dids;
-  int* rec_pin = nullptr;
-  unsigned fetched = 0;
-  int replayed = 0, longest_prefix = 0;
-  // the tracks' pixel lists (seg_tracks.hip), created by the first ddlo_seg_tracks_sync
-  SegTracks* tracks = nullptr;
-  // the per-pixel classes (seg_classes.hip), created by the first ddlo_seg_classify;
-  // scan_serial: counts the scans handed in, so that a class image is known to be of the last one
-  SegClasses* classes = nullptr;
-  unsigned long long scan_serial = 0;
-  // the projection of unorganized clouds (seg_project.hip), created by the first projected scan
-  SegProject* project = nullptr;
-};
-
 // the pinned record: the ints and the first averages in one copy
 constexpr size_t kRecPinBytes = kLabelRecMinBytes;
 constexpr size_t kRecPinAvg = (kRecPinBytes - sizeof(int) * kLabelRecInts) / sizeof(double);
-enum : unsigned { kImgRange = 1, kImgGround = 2, kImgLabel = 4 };
 
-// device mode: the host images a getter needs, read back once per scan
-static gicp_status fetch_images(ddlo_seg* o, unsigned want) {
+namespace ddlo {
+
+gicp_status fetch_images(ddlo_seg* o, unsigned want) {
   if (o->labelling != DDLO_SEG_LABEL_DEVICE) return GICP_OK;
   const unsigned need = want & ~o->fetched;
   if (!need) return GICP_OK;
@@ -618,6 +536,8 @@ static gicp_status fetch_images(ddlo_seg* o, unsigned want) {
   o->fetched |= need;
   return GICP_OK;
 }
+
+}  // namespace ddlo
 
 extern "C" {
 
@@ -658,10 +578,8 @@ gicp_status ddlo_seg_create(int device, const ddlo_seg_params* p, ddlo_seg** out
   HIP_TRY(hipSetDevice(device));
   HIP_TRY(hipStreamCreateWithFlags(&o->s, hipStreamNonBlocking));
   const size_t n = (size_t)o->p.rows * o->p.cols;
-  o->pin_bytes = n * (sizeof(float) + sizeof(int) + sizeof(float)) + n;
-  if (hipHostMalloc((void**)&o->pin, o->pin_bytes, hipHostMallocDefault) != hipSuccess ||
-      hipHostMalloc((void**)&o->cnt_pin, sizeof(int) * 16, hipHostMallocDefault) != hipSuccess) {
-    if (o->pin) (void)hipHostFree(o->pin);
+  if (o->pin.reset(n * (sizeof(float) + sizeof(int) + sizeof(float)) + n) != hipSuccess ||
+      o->cnt_pin.reset(sizeof(int) * 16) != hipSuccess) {
     (void)hipStreamDestroy(o->s);
     return fail(GICP_EHIP, "pinned allocation failed");
   }
@@ -673,20 +591,91 @@ gicp_status ddlo_seg_destroy(ddlo_seg* s) {
   if (!s) return GICP_OK;
   (void)hipSetDevice(s->device);
   (void)hipStreamSynchronize(s->s);
-  s->raw.reset();
-  s->range.reset();
-  s->ground.reset();
-  s->label.reset();
-  if (s->pin) (void)hipHostFree(s->pin);
-  if (s->cnt_pin) (void)hipHostFree(s->cnt_pin);
-  if (s->rec_pin) (void)hipHostFree(s->rec_pin);
-  s->obj_stage.release();
-  s->drop_stage.release();
-  seg_tracks_free(s->tracks);
-  seg_classes_free(s->classes);
-  seg_project_free(s->project);
   (void)hipStreamDestroy(s->s);
-  delete s;
+  delete s;   // (the buffers and the parts: their owners' destructors)
+  return GICP_OK;
+}
+
+}  // extern "C"
+
+// the pinned read-back images of a handle: range | label | z (staged scans) | ground
+struct HostImages {
+  float* range;
+  int* label;
+  float* z;
+  signed char* ground;
+};
+static HostImages host_images(const ddlo_seg* o, size_t n) {
+  HostImages h;
+  h.range = o->pin.as<float>();
+  h.label = reinterpret_cast<int*>(h.range + n);
+  h.z = reinterpret_cast<float*>(h.label + n);
+  h.ground = reinterpret_cast<signed char*>(h.z + n);
+  return h;
+}
+
+// seg_run's tail in device mode: the labelling reads z from the scan itself;
+// only the record comes back: the counts and the first averages, then the
+// other averages if there are more
+static gicp_status label_tail_device(ddlo_seg* o, size_t n, const float T[16], const float* residual, ddlo_seg_result* r) {
+  const float* dres = nullptr;
+  if (residual) {
+    HIP_TRY(rt::grow(o->dresid, sizeof(float) * n, o->s));
+    HIP_TRY(hipMemcpyAsync(o->dresid.p, residual, sizeof(float) * n, hipMemcpyHostToDevice, o->s));
+    dres = o->dresid.as<float>();
+  }
+  const LabelDevIn in{o->range.as<float>(), o->raw.as<unsigned char>() + 8, o->raw_stride, dres,
+                      o->ground.as<signed char>(), o->label.as<int>(), T[11]};
+  if (gicp_status st = label_device_run(o->s, o->p, o->ldev, in)) return st;
+  HIP_TRY(hipMemcpyAsync(o->rec_pin.p, o->ldev.rec.p, kRecPinBytes, hipMemcpyDeviceToHost, o->s));
+  HIP_TRY(hipStreamSynchronize(o->s));
+  const int* ri = o->rec_pin.as<int>();
+  if (ri[kRecError]) return fail(GICP_EHIP, "device labelling: a replay queue left its component's range");
+  const size_t navg = (size_t)ri[kRecSegments] + 1;
+  o->avg.assign(navg, 0.0);
+  const double* pavg = reinterpret_cast<const double*>(ri + kLabelRecInts);
+  for (size_t l = 0; l < navg && l < kRecPinAvg; ++l) o->avg[l] = pavg[l];
+  if (navg > kRecPinAvg) {
+    HIP_TRY(hipMemcpyAsync(o->avg.data() + kRecPinAvg, o->ldev.avg() + kRecPinAvg, sizeof(double) * (navg - kRecPinAvg),
+                           hipMemcpyDeviceToHost, o->s));
+    HIP_TRY(hipStreamSynchronize(o->s));
+  }
+  o->fetched = 0;
+  o->replayed = ri[kRecReplayed];
+  o->longest_prefix = ri[kRecLongestPrefix];
+  *r = ddlo_seg_result{ri[kRecSegments], ri[kRecGround], ri[kRecRange], ri[kRecRejected]};
+  return GICP_OK;
+}
+
+// seg_run's tail in host mode: the images come back and the reference's search
+// runs over them.  It reads cloud_in_t z (:629): gathered from xyz_t while the
+// device works, or (a staged scan) read back with the images from o->zimg.
+static gicp_status label_tail_host(ddlo_seg* o, size_t n, const HostImages& h, const float* xyz_t, const float T[16],
+                                   const float* residual, ddlo_seg_result* r) {
+  HIP_TRY(hipMemcpyAsync(h.range, o->range.p, sizeof(float) * n, hipMemcpyDeviceToHost, o->s));
+  HIP_TRY(hipMemcpyAsync(h.label, o->label.p, sizeof(int) * n, hipMemcpyDeviceToHost, o->s));
+  HIP_TRY(hipMemcpyAsync(h.ground, o->ground.p, n, hipMemcpyDeviceToHost, o->s));
+  const float* zsrc = h.z;
+  if (xyz_t) {
+    o->z.resize(n);
+    const unsigned char* b = reinterpret_cast<const unsigned char*>(xyz_t);
+    const size_t stride = o->raw_stride;
+    for (size_t i = 0; i < n; ++i) std::memcpy(&o->z[i], b + i * stride + 8, sizeof(float));
+    zsrc = o->z.data();
+  } else {
+    HIP_TRY(hipMemcpyAsync(h.z, o->zimg.p, sizeof(float) * n, hipMemcpyDeviceToHost, o->s));
+  }
+  HIP_TRY(hipStreamSynchronize(o->s));
+  Labeller lb(o->p, h.range, zsrc, residual, h.label, T[11], o->avg, o->work);
+  lb.run();
+  ddlo_seg_result c{};   // (a local: the counting loop keeps its sums in registers)
+  c.segments = lb.label_count - 1;
+  for (size_t i = 0; i < n; ++i) {
+    c.ground_pixels += h.ground[i] == 1;
+    c.range_pixels += h.range[i] > 0.f;
+    c.rejected_pixels += h.label[i] == kRejected;
+  }
+  *r = c;
   return GICP_OK;
 }
 
@@ -697,8 +686,9 @@ static gicp_status seg_run(ddlo_seg* o, const float* xyz_t, size_t stride, const
   const int H = p.rows, W = p.cols;
   const size_t n = (size_t)H * W;
   HIP_TRY(hipSetDevice(o->device));
-  o->have = false;
+  o->have = false;   // until the end: every error return leaves the handle without a scan
   o->have_objects = false;
+  o->csr_ready = o->csr_len_ready = false;
   ++o->scan_serial;
   const size_t raw_sz = (n - 1) * stride + 12;
   HIP_TRY(o->raw.ensure(raw_sz));
@@ -707,8 +697,11 @@ static gicp_status seg_run(ddlo_seg* o, const float* xyz_t, size_t stride, const
   HIP_TRY(o->ground.ensure(n));
   HIP_TRY(o->label.ensure(sizeof(int) * n));
   const bool dev_label = o->labelling == DDLO_SEG_LABEL_DEVICE;
+  // a staged scan's z reaches the host labelling as an image of its own
+  // (xyz_t: gathered on the host; device labelling: read from the scan)
+  const bool z_image = !xyz_t && !dev_label;
   if (xyz_t) HIP_TRY(hipMemcpyAsync(o->raw.p, xyz_t, raw_sz, hipMemcpyHostToDevice, o->s));
-  else if (!dev_label) HIP_TRY(o->zimg.ensure(sizeof(float) * n));
+  if (z_image) HIP_TRY(o->zimg.ensure(sizeof(float) * n));
   SegPixelArgs a{};
   a.raw = o->raw.as<unsigned char>();
   a.stride = stride;
@@ -724,84 +717,25 @@ static gicp_status seg_run(ddlo_seg* o, const float* xyz_t, size_t stride, const
   a.range = o->range.as<float>();
   a.ground = o->ground.as<signed char>();
   a.label = o->label.as<int>();
-  a.zout = (xyz_t || dev_label) ? nullptr : o->zimg.as<float>();
+  a.zout = z_image ? o->zimg.as<float>() : nullptr;
   k_seg_pixels<<<dim3(cdiv_s(W, 256), H), 256, 0, o->s>>>(a);
   HIP_TRY(hipGetLastError());
-  float* pin_range = o->pin;
-  int* pin_label = reinterpret_cast<int*>(o->pin + n);
-  float* pin_z = reinterpret_cast<float*>(pin_label + n);
-  signed char* pin_ground = reinterpret_cast<signed char*>(pin_z + n);
-  if (dev_label) {
-    // the labelling reads z from the scan itself; only the record comes back:
-    // the counts and the first averages, then the other averages if there are more
-    const float* dres = nullptr;
-    if (residual) {
-      HIP_TRY(rt::grow(o->dresid, sizeof(float) * n, o->s));
-      HIP_TRY(hipMemcpyAsync(o->dresid.p, residual, sizeof(float) * n, hipMemcpyHostToDevice, o->s));
-      dres = o->dresid.as<float>();
-    }
-    const LabelDevIn in{o->range.as<float>(), o->raw.as<unsigned char>() + 8, stride, dres, o->ground.as<signed char>(),
-                        o->label.as<int>(), T[11]};
-    if (gicp_status st = label_device_run(o->s, p, o->ldev, in)) return st;
-    HIP_TRY(hipMemcpyAsync(o->rec_pin, o->ldev.rec.p, kRecPinBytes, hipMemcpyDeviceToHost, o->s));
-    HIP_TRY(hipStreamSynchronize(o->s));
-    const int* ri = o->rec_pin;
-    if (ri[kRecError]) return fail(GICP_EHIP, "device labelling: a replay queue left its component's range");
-    const size_t navg = (size_t)ri[kRecSegments] + 1;
-    o->avg.assign(navg, 0.0);
-    const double* pavg = reinterpret_cast<const double*>(ri + kLabelRecInts);
-    for (size_t l = 0; l < navg && l < kRecPinAvg; ++l) o->avg[l] = pavg[l];
-    if (navg > kRecPinAvg) {
-      HIP_TRY(hipMemcpyAsync(o->avg.data() + kRecPinAvg, o->ldev.avg() + kRecPinAvg, sizeof(double) * (navg - kRecPinAvg),
-                             hipMemcpyDeviceToHost, o->s));
-      HIP_TRY(hipStreamSynchronize(o->s));
-    }
-    o->h_range = pin_range;
-    o->h_ground = pin_ground;
-    o->h_label = pin_label;
-    o->hn = n;
-    o->fetched = 0;
-    o->replayed = ri[kRecReplayed];
-    o->longest_prefix = ri[kRecLongestPrefix];
-    ddlo_seg_result r{ri[kRecSegments], ri[kRecGround], ri[kRecRange], ri[kRecRejected]};
-    o->last = r;
-    o->have = true;
-    if (res) *res = r;
-    return GICP_OK;
-  }
-  HIP_TRY(hipMemcpyAsync(pin_range, o->range.p, sizeof(float) * n, hipMemcpyDeviceToHost, o->s));
-  HIP_TRY(hipMemcpyAsync(pin_label, o->label.p, sizeof(int) * n, hipMemcpyDeviceToHost, o->s));
-  HIP_TRY(hipMemcpyAsync(pin_ground, o->ground.p, n, hipMemcpyDeviceToHost, o->s));
-  // the labelling reads cloud_in_t z (:629); gathered while the device works
-  // (a staged scan's comes back with the images)
-  const float* zsrc = pin_z;
-  if (xyz_t) {
-    o->z.resize(n);
-    const unsigned char* b = reinterpret_cast<const unsigned char*>(xyz_t);
-    for (size_t i = 0; i < n; ++i) std::memcpy(&o->z[i], b + i * stride + 8, sizeof(float));
-    zsrc = o->z.data();
-  } else {
-    HIP_TRY(hipMemcpyAsync(pin_z, o->zimg.p, sizeof(float) * n, hipMemcpyDeviceToHost, o->s));
-  }
-  HIP_TRY(hipStreamSynchronize(o->s));
-  o->h_range = pin_range;
-  o->h_ground = pin_ground;
-  o->h_label = pin_label;
-  o->hn = n;
-  Labeller lb(p, o->h_range, zsrc, residual, o->h_label, T[11], o->avg, o->work);
-  lb.run();
+  const HostImages h = host_images(o, n);
   ddlo_seg_result r{};
-  r.segments = lb.label_count - 1;
-  for (size_t i = 0; i < n; ++i) {
-    r.ground_pixels += o->h_ground[i] == 1;
-    r.range_pixels += o->h_range[i] > 0.f;
-    r.rejected_pixels += o->h_label[i] == kRejected;
-  }
+  if (gicp_status st = dev_label ? label_tail_device(o, n, T, residual, &r)
+                                 : label_tail_host(o, n, h, xyz_t, T, residual, &r))
+    return st;
+  o->h_range = h.range;
+  o->h_ground = h.ground;
+  o->h_label = h.label;
+  o->hn = n;
   o->last = r;
   o->have = true;
   if (res) *res = r;
   return GICP_OK;
 }
+
+extern "C" {
 
 gicp_status ddlo_seg_process(ddlo_seg* o, const float* xyz_t, size_t stride, const float T[16], const float* residual,
                              ddlo_seg_result* res) {
@@ -854,23 +788,14 @@ gicp_status ddlo_seg_label_indices(ddlo_seg* o, int32_t* offsets, size_t offsets
   if (gicp_status st = fetch_images(o, kImgLabel)) return st;
   const int L = o->last.segments;
   if (offsets && offsets_cap < (size_t)L + 2) return fail(GICP_EINVAL, "offsets needs segments + 2 entries");
-  std::vector<int32_t> cnt(L + 2, 0);
-  const size_t n = o->hn;
-  for (size_t i = 0; i < n; ++i) {
-    const int l = o->h_label[i];
-    if (l > 0 && l != kRejected) ++cnt[l + 1];
-  }
-  for (int l = 1; l <= L + 1; ++l) cnt[l] += cnt[l - 1];
+  std::vector<int32_t> cnt;
+  label_csr_offsets(o->h_label, o->hn, L, cnt);
   const size_t total = (size_t)cnt[L + 1];
   if (n_indices) *n_indices = total;
   if (offsets) std::memcpy(offsets, cnt.data(), sizeof(int32_t) * (L + 2));
   if (indices) {
     if (indices_cap < total) return fail(GICP_EINVAL, "indices buffer too small");
-    std::vector<int32_t> pos(cnt.begin(), cnt.end() - 1);
-    for (size_t i = 0; i < n; ++i) {   // row-major within a label, as :527-537
-      const int l = o->h_label[i];
-      if (l > 0 && l != kRejected) indices[pos[l]++] = (int32_t)i;
-    }
+    label_csr_pixels(o->h_label, o->hn, cnt, indices);
   }
   return GICP_OK;
 }
@@ -917,128 +842,85 @@ gicp_status seg_process_staged(ddlo_seg* o, const float T[16], const float* resi
   return seg_run(o, nullptr, sizeof(float4), T, residual, res);
 }
 
+// The last scan's L >= 1 segments as CSR on the device.  Device labelling: the
+// labelling's own.  Host labelling: the labelling's lists joined and sent up
+// into dcsr (enqueued, not waited for), once per scan, by whoever asks first;
+// the rows are staged in obj_stage, which is sized here for the records that
+// ddlo_seg_objects reads back behind them, so it does not move while the copy runs.
+static gicp_status csr_pointers(ddlo_seg* o, const int** off, const int** pix) {
+  if (o->labelling == DDLO_SEG_LABEL_DEVICE) {
+    *off = o->ldev.off();
+    *pix = o->ldev.pixels();
+    return GICP_OK;
+  }
+  const int L = o->last.segments;
+  if (!o->csr_ready) {
+    HIP_TRY(o->obj_stage.ensure(rec_offset(o->work.seg_off, L) + sizeof(ddlo_seg_object) * (size_t)L));
+    if (gicp_status st = upload_csr(o->s, o->work.seg_off, o->work.seg_pix, L, o->dcsr, o->obj_stage.as<int>())) return st;
+    o->csr_ready = true;
+  }
+  *off = o->dcsr.as<int>();
+  *pix = o->dcsr.as<int>() + L + 2;
+  return GICP_OK;
+}
+
+gicp_status seg_csr(ddlo_seg* o, SegCsr* out) {
+  if (!o || !out) return fail(GICP_EINVAL, "null argument");
+  if (!o->have) return fail(GICP_EINVAL, "no processed scan");
+  const int L = o->last.segments;
+  *out = SegCsr{};
+  out->L = L;
+  if (L > 0) {
+    HIP_TRY(hipSetDevice(o->device));
+    if (gicp_status st = csr_pointers(o, &out->d_off, &out->d_pix)) return st;
+  }
+  if (!o->csr_len_ready) {
+    std::vector<int>& len = o->csr_len;
+    len.assign((size_t)L + 1, 0);
+    if (o->labelling != DDLO_SEG_LABEL_DEVICE) {
+      for (int l = 1; l <= L; ++l) len[l] = o->work.seg_off[l + 1] - o->work.seg_off[l];
+    } else if (o->have_objects) {   // the object records carry every segment's length
+      for (int l = 1; l <= L; ++l) len[l] = o->objects[(size_t)l - 1].num_points;
+    } else if (L > 0) {
+      std::vector<int> off((size_t)L + 2);
+      HIP_TRY(hipMemcpyAsync(off.data(), o->ldev.off(), sizeof(int) * off.size(), hipMemcpyDeviceToHost, o->s));
+      HIP_TRY(hipStreamSynchronize(o->s));
+      for (int l = 1; l <= L; ++l) len[l] = off[l + 1] - off[l];
+    }
+    o->csr_len_ready = true;
+  }
+  out->len = o->csr_len.data();
+  return GICP_OK;
+}
+
 gicp_status seg_objects_vec(ddlo_seg* o, float max_dim_ratio, std::vector<ddlo_seg_object>& out) {
   if (!o) return fail(GICP_EINVAL, "null handle");
   if (!o->have) return fail(GICP_EINVAL, "no processed scan");
   HIP_TRY(hipSetDevice(o->device));
   if (!o->have_objects) {
-    gicp_status st = o->labelling == DDLO_SEG_LABEL_DEVICE
-                         ? run_objects_dev(o->s, o->raw.as<unsigned char>(), o->raw_stride, o->ldev.off(), o->ldev.pixels(),
-                                           o->last.segments, o->dobj, o->objects, o->obj_stage)
-                         : run_objects(o->s, o->raw.as<unsigned char>(), o->raw_stride, o->work.seg_off, o->work.seg_pix,
-                                 o->last.segments, o->dcsr, o->dobj, o->objects, &o->obj_stage);
-    if (st) return st;
+    const int L = o->last.segments;
+    o->objects.assign((size_t)L, ddlo_seg_object{});
+    if (L > 0) {
+      // the records come back through obj_stage: behind the rows it staged (host labelling), or at its start
+      const bool dev_label = o->labelling == DDLO_SEG_LABEL_DEVICE;
+      if (dev_label) HIP_TRY(o->obj_stage.ensure(sizeof(ddlo_seg_object) * (size_t)L));
+      const int *off = nullptr, *pix = nullptr;
+      if (gicp_status st = csr_pointers(o, &off, &pix)) return st;
+      void* const rec_pin = o->obj_stage.as<char>() + (dev_label ? 0 : rec_offset(o->work.seg_off, L));
+      if (gicp_status st = run_objects(o->s, o->raw.as<unsigned char>(), o->raw_stride, off, pix, L, o->dobj, o->objects, rec_pin))
+        return st;
+    }
     o->have_objects = true;
   }
   filter_objects(o->objects, o->avg.data(), o->avg.size(), max_dim_ratio, out);
   return GICP_OK;
 }
 
-gicp_status seg_static_cloud_dev(ddlo_seg* o, const int32_t* remove_ids, size_t n_remove, const float centre[3],
-                                 double crop_size, double leaf, const float4** pts, int* count) {
-  return seg_static_cloud_with(o, remove_ids, n_remove, centre, crop_size, leaf, pts, count, nullptr);
-}
-
-gicp_status seg_tracks_view(ddlo_seg* o, SegTrackView* v, bool with_csr) {
-  if (!o || !v) return fail(GICP_EINVAL, "null argument");
-  v->device = o->device;
-  v->stream = o->s;
-  v->npix = o->p.rows * o->p.cols;
-  v->have = o->have;
-  v->segments = o->have ? o->last.segments : 0;
-  v->slot = &o->tracks;
-  v->d_off = v->d_pix = nullptr;
-  v->len.assign((size_t)v->segments + 1, 0);
-  const int L = v->segments;
-  if (L <= 0 || !with_csr) return GICP_OK;
-  HIP_TRY(hipSetDevice(o->device));
-  if (o->labelling == DDLO_SEG_LABEL_DEVICE) {
-    v->d_off = o->ldev.off();
-    v->d_pix = o->ldev.pixels();
-    if (o->have_objects) {   // the object records carry every segment's length
-      for (int l = 1; l <= L; ++l) v->len[l] = o->objects[(size_t)l - 1].num_points;
-    } else {
-      std::vector<int> off((size_t)L + 2);
-      HIP_TRY(hipMemcpyAsync(off.data(), o->ldev.off(), sizeof(int) * off.size(), hipMemcpyDeviceToHost, o->s));
-      HIP_TRY(hipStreamSynchronize(o->s));
-      for (int l = 1; l <= L; ++l) v->len[l] = off[l + 1] - off[l];
-    }
-    return GICP_OK;
-  }
-  const std::vector<int>& off = o->work.seg_off;
-  const size_t noff = (size_t)L + 2, npix = (size_t)off[L + 1];
-  if (!o->have_objects) {   // the upload run_objects makes for k_seg_objects has not happened for this scan
-    std::vector<int> joined(noff + npix);
-    std::memcpy(joined.data(), off.data(), sizeof(int) * noff);
-    if (npix) std::memcpy(joined.data() + noff, o->work.seg_pix.data(), sizeof(int) * npix);
-    HIP_TRY(o->dcsr.ensure(sizeof(int) * joined.size()));
-    HIP_TRY(hipMemcpyAsync(o->dcsr.p, joined.data(), sizeof(int) * joined.size(), hipMemcpyHostToDevice, o->s));
-    HIP_TRY(hipStreamSynchronize(o->s));
-  }
-  v->d_off = o->dcsr.as<int>();
-  v->d_pix = o->dcsr.as<int>() + noff;
-  for (int l = 1; l <= L; ++l) v->len[l] = off[l + 1] - off[l];
-  return GICP_OK;
-}
-
-gicp_status seg_classes_view(ddlo_seg* o, SegClassView* v) {
-  if (!o || !v) return fail(GICP_EINVAL, "null argument");
-  v->device = o->device;
-  v->stream = o->s;
-  v->rows = o->p.rows;
-  v->cols = o->p.cols;
-  v->ground_rows = o->p.ground_rows;
-  v->have = o->have;
-  v->serial = o->scan_serial;
-  v->raw = o->raw.as<unsigned char>();
-  v->stride = o->raw_stride;
-  v->ground = o->ground.as<signed char>();
-  v->slot = &o->classes;
-  return GICP_OK;
-}
-
-gicp_status seg_project_view(ddlo_seg* o, SegProjView* v) {
-  if (!o || !v) return fail(GICP_EINVAL, "null argument");
-  v->device = o->device;
-  v->stream = o->s;
-  v->params = o->p;
-  v->have = o->have;
-  v->serial = o->scan_serial;
-  v->slot = &o->project;
-  return GICP_OK;
-}
-
-gicp_status seg_static_cloud_with(ddlo_seg* o, const int32_t* remove_ids, size_t n_remove, const float centre[3],
-                                  double crop_size, double leaf, const float4** pts, int* count,
-                                  const SegDropHook* more) {
-  if (!o || !pts || !count || !centre || (!remove_ids && n_remove)) return fail(GICP_EINVAL, "invalid argument");
+gicp_status seg_static_begin(ddlo_seg* o, const float centre[3], const float4** pts, int* count) {
+  if (!o || !pts || !count || !centre) return fail(GICP_EINVAL, "invalid argument");
   if (!o->have) return fail(GICP_EINVAL, "no processed scan");
-  const int L = o->last.segments;
-  const bool dev_label = o->labelling == DDLO_SEG_LABEL_DEVICE;
-  const std::vector<int>& off = o->work.seg_off;
-  size_t ndrop = 0;
-  for (size_t k = 0; k < n_remove; ++k) {
-    if (remove_ids[k] < 1 || remove_ids[k] > L) return fail(GICP_EINVAL, "remove_ids names no segment of the last scan");
-    if (!dev_label) ndrop += (size_t)(off[remove_ids[k] + 1] - off[remove_ids[k]]);
-  }
   HIP_TRY(hipSetDevice(o->device));
   const int n = (int)o->hn;
-  // the removed segments' pixels (an id named twice is listed twice: harmless);
-  // device labelling: only their ids go up, the pixel lists are on the device
-  const size_t stage_ints = dev_label ? n_remove : ndrop;
-  if (gicp_status st = o->drop_stage.ensure(sizeof(int) * std::max<size_t>(stage_ints, 1))) return st;
-  int* const drop = static_cast<int*>(o->drop_stage.p);
-  size_t w = 0;
-  for (size_t k = 0; k < n_remove; ++k) {
-    if (dev_label) {
-      drop[w++] = remove_ids[k];
-      continue;
-    }
-    const int b = off[remove_ids[k]], e = off[remove_ids[k] + 1];
-    std::memcpy(drop + w, o->work.seg_pix.data() + b, sizeof(int) * (size_t)(e - b));
-    w += (size_t)(e - b);
-  }
-  HIP_TRY(o->ddrop.ensure(sizeof(int) * std::max<size_t>(ndrop, 1)));
   HIP_TRY(o->f4.ensure(sizeof(float4) * (size_t)n));
   HIP_TRY(o->f4b.ensure(sizeof(float4) * (size_t)n));
   HIP_TRY(o->keep.ensure(sizeof(int) * (size_t)n));
@@ -1046,29 +928,23 @@ gicp_status seg_static_cloud_with(ddlo_seg* o, const int32_t* remove_ids, size_t
   HIP_TRY(o->vscratch.ensure(sizeof(int) * voxel_scratch_ints(n)));
   HIP_TRY(o->cubtmp.ensure(std::max(crop_box_tmp_bytes(n), voxel_tmp_bytes(n))));
   launch_pack4(o->s, o->raw.as<unsigned char>(), o->raw_stride, n, o->f4.as<float4>());
-  if (dev_label && n_remove) {
-    HIP_TRY(rt::grow(o->dids, sizeof(int) * n_remove, o->s));
-    HIP_TRY(hipMemcpyAsync(o->dids.p, drop, sizeof(int) * n_remove, hipMemcpyHostToDevice, o->s));
-    if (gicp_status st = label_device_drop(o->s, o->ldev, o->dids.as<int>(), (int)n_remove, o->f4.as<float4>())) return st;
-  }
-  if (ndrop) {
-    HIP_TRY(hipMemcpyAsync(o->ddrop.p, drop, sizeof(int) * ndrop, hipMemcpyHostToDevice, o->s));
-    k_static_drop<<<cdiv_s((long)ndrop, 256), 256, 0, o->s>>>(o->ddrop.as<int>(), (int)ndrop, o->f4.as<float4>());
-  }
-  HIP_TRY(hipGetLastError());
-  if (more && *more)
-    if (gicp_status st = (*more)(o->s, o->f4.as<float4>(), n)) return st;
+  return GICP_OK;
+}
+
+gicp_status seg_static_finish(ddlo_seg* o, const float centre[3], double crop_size, double leaf, const float4** pts,
+                              int* count) {
+  const int n = (int)o->hn;
   const CropCentre cc{centre[0], centre[1], centre[2]};
   const bool crop = crop_size > 0;
   int m = -1;
   if (leaf > 0) {   // the crop box folded into the voxel pass (as the driver's preprocessing does)
     if (voxel_grid(o->s, o->f4.as<float4>(), n, (float)leaf, o->f4b.as<float4>(), o->vscratch.as<int>(), o->cubtmp.p,
-                   o->cubtmp.bytes, &m, crop ? (float)crop_size : 0.f, o->cnt_pin, cc))
+                   o->cubtmp.bytes, &m, crop ? (float)crop_size : 0.f, o->cnt_pin.as<int>(), cc))
       return fail(GICP_EHIP, "voxel filter scratch too small");
   }
   if (m < 0) {   // no voxel filter, or its grid overflows (the reference then keeps the cloud as it is)
     if (crop_box(o->s, o->f4.as<float4>(), n, (float)crop_size, o->f4b.as<float4>(), o->keep.as<int>(), o->pos.as<int>(),
-                 o->cubtmp.p, o->cubtmp.bytes, &m, o->cnt_pin, cc, crop))
+                 o->cubtmp.p, o->cubtmp.bytes, &m, o->cnt_pin.as<int>(), cc, crop))
       return fail(GICP_EHIP, "crop box scratch too small");
   }
   HIP_TRY(hipGetLastError());
@@ -1076,6 +952,45 @@ gicp_status seg_static_cloud_with(ddlo_seg* o, const int32_t* remove_ids, size_t
   *pts = o->f4b.as<float4>();
   *count = m;
   return GICP_OK;
+}
+
+// the removal by segment id.  Host labelling: the removed segments' pixels go
+// up (an id named twice is listed twice: harmless); device labelling: only
+// their ids, the pixel lists are on the device.  Both through drop_stage.
+gicp_status seg_static_cloud_dev(ddlo_seg* o, const int32_t* remove_ids, size_t n_remove, const float centre[3],
+                                 double crop_size, double leaf, const float4** pts, int* count) {
+  if (!o || !pts || !count || !centre || (!remove_ids && n_remove)) return fail(GICP_EINVAL, "invalid argument");
+  if (!o->have) return fail(GICP_EINVAL, "no processed scan");
+  const bool dev_label = o->labelling == DDLO_SEG_LABEL_DEVICE;
+  const std::vector<int>& off = o->work.seg_off;
+  size_t ndrop = 0;
+  for (size_t k = 0; k < n_remove; ++k) {
+    if (remove_ids[k] < 1 || remove_ids[k] > o->last.segments)
+      return fail(GICP_EINVAL, "remove_ids names no segment of the last scan");
+    if (!dev_label) ndrop += (size_t)(off[remove_ids[k] + 1] - off[remove_ids[k]]);
+  }
+  if (gicp_status st = seg_static_begin(o, centre, pts, count)) return st;
+  HIP_TRY(o->drop_stage.ensure(sizeof(int) * std::max<size_t>(dev_label ? n_remove : ndrop, 1)));
+  int* const drop = o->drop_stage.as<int>();
+  if (dev_label && n_remove) {
+    std::memcpy(drop, remove_ids, sizeof(int) * n_remove);
+    HIP_TRY(rt::grow(o->dids, sizeof(int) * n_remove, o->s));
+    HIP_TRY(hipMemcpyAsync(o->dids.p, drop, sizeof(int) * n_remove, hipMemcpyHostToDevice, o->s));
+    if (gicp_status st = label_device_drop(o->s, o->ldev, o->dids.as<int>(), (int)n_remove, o->f4.as<float4>())) return st;
+  }
+  if (ndrop) {
+    size_t w = 0;
+    for (size_t k = 0; k < n_remove; ++k) {
+      const int b = off[remove_ids[k]], e = off[remove_ids[k] + 1];
+      std::memcpy(drop + w, o->work.seg_pix.data() + b, sizeof(int) * (size_t)(e - b));
+      w += (size_t)(e - b);
+    }
+    HIP_TRY(o->ddrop.ensure(sizeof(int) * ndrop));
+    HIP_TRY(hipMemcpyAsync(o->ddrop.p, drop, sizeof(int) * ndrop, hipMemcpyHostToDevice, o->s));
+    k_static_drop<<<cdiv_s((long)ndrop, 256), 256, 0, o->s>>>(o->ddrop.as<int>(), (int)ndrop, o->f4.as<float4>());
+  }
+  HIP_TRY(hipGetLastError());
+  return seg_static_finish(o, centre, crop_size, leaf, pts, count);
 }
 
 }  // namespace ddlo
@@ -1107,21 +1022,23 @@ gicp_status ddlo_seg_objects_from(int device, const float* xyz_t, size_t stride,
   int L = 0;
   for (size_t i = 0; i < np; ++i)
     if (label[i] > L && label[i] != kRejected) L = label[i];
-  std::vector<int> off((size_t)L + 2, 0);
-  for (size_t i = 0; i < np; ++i)
-    if (label[i] > 0 && label[i] != kRejected) ++off[label[i] + 1];
-  for (int l = 1; l <= L + 1; ++l) off[l] += off[l - 1];
-  std::vector<int> pix((size_t)off[L + 1]), at(off.begin(), off.end() - 1);
-  for (size_t i = 0; i < np; ++i)
-    if (label[i] > 0 && label[i] != kRejected) pix[at[label[i]]++] = (int)i;
+  std::vector<int> off;
+  label_csr_offsets(label, np, L, off);
+  std::vector<int> pix((size_t)off[L + 1]);
+  label_csr_pixels(label, np, off, pix.data());
   DevBuf raw, dcsr, dobj;
   const size_t raw_sz = (np - 1) * stride + 12;
   HIP_TRY(raw.ensure(raw_sz));
   hipStream_t s = nullptr;   // the null stream: the copy below is synchronous with it
   HIP_TRY(hipMemcpy(raw.p, xyz_t, raw_sz, hipMemcpyHostToDevice));
-  std::vector<ddlo_seg_object> recs, v;
-  gicp_status st = run_objects(s, raw.as<unsigned char>(), stride, off, pix, L, dcsr, dobj, recs, nullptr);
-  if (st) return st;
+  std::vector<ddlo_seg_object> recs((size_t)L), v;
+  if (L > 0) {   // pageable staging both ways
+    std::vector<int> rows(off.size() + pix.size());
+    if (gicp_status st = upload_csr(s, off, pix, L, dcsr, rows.data())) return st;
+    if (gicp_status st = run_objects(s, raw.as<unsigned char>(), stride, dcsr.as<int>(), dcsr.as<int>() + off.size(), L, dobj,
+                                     recs, nullptr))
+      return st;
+  }
   filter_objects(recs, avg_residual, avg_residual ? avg_n : 0, max_dim_ratio, v);
   for (size_t i = 0; i < v.size() && i < cap; ++i) out[i] = v[i];
   *n = v.size();
@@ -1138,15 +1055,7 @@ gicp_status ddlo_seg_static_cloud(ddlo_seg* o, const int32_t* remove_ids, size_t
   *nout = (size_t)m;
   if (!out || m == 0) return GICP_OK;
   if ((size_t)m > cap) return fail(GICP_EINVAL, "output capacity too small");
-  std::vector<float4> h((size_t)m);
-  HIP_TRY(hipMemcpyAsync(h.data(), pts, sizeof(float4) * (size_t)m, hipMemcpyDeviceToHost, o->s));
-  HIP_TRY(hipStreamSynchronize(o->s));
-  for (int i = 0; i < m; ++i) {
-    out[3 * i] = h[i].x;
-    out[3 * i + 1] = h[i].y;
-    out[3 * i + 2] = h[i].z;
-  }
-  return GICP_OK;
+  return rt::read_xyz(o->s, pts, (size_t)m, out);
 }
 
 }  // extern "C"
@@ -1159,14 +1068,15 @@ gicp_status ddlo_seg_set_labelling(ddlo_seg* o, int mode) {
   if (mode == DDLO_SEG_LABEL_DEVICE) {
     if (!label_device_window_ok(o->p))
       return fail(GICP_EINVAL, "device labelling needs 0 <= win_col0 and win_col1 <= cols - 1");
-    if (!o->rec_pin) {
+    if (!o->rec_pin.p) {
       HIP_TRY(hipSetDevice(o->device));
-      HIP_TRY(hipHostMalloc((void**)&o->rec_pin, kRecPinBytes, hipHostMallocDefault));
+      HIP_TRY(o->rec_pin.reset(kRecPinBytes));
     }
   }
   if (mode != o->labelling) {   // the last scan's results belong to the other mode's data
     o->have = false;
     o->have_objects = false;
+    o->csr_ready = o->csr_len_ready = false;
   }
   o->labelling = mode;
   return GICP_OK;

@@ -185,6 +185,89 @@ def test_pool_lists_stale_removal_and_growth(mode, H, sizes):
     seg.close()
 
 
+def all_tracks(segments):
+    """every segment l of the last scan as track 100 + l"""
+    return [(100 + l, l) for l in range(1, segments + 1)]
+
+
+@pytest.mark.parametrize("mode", ["host", "device"])
+def test_segments_csr_made_once_by_whoever_asks_first(mode):
+    """The last scan's segments reach the device once per scan, for the tracks or for the objects, whichever
+    asks first: both orders give the same lists and records, and a new scan never meets the old lists."""
+    H = 16
+    xyz0, _ = synth_scan(H, SMALL, 11)
+    xyz1, _ = synth_scan(H, SMALL[::-1], 12)           # segment l has another length than in scan 0
+    a = S.Segmentation(0, synth_params(H), labelling=mode)
+    b = S.Segmentation(0, synth_params(H), labelling=mode)
+    n = a.process(xyz0, EYE).segments
+    assert n == len(SMALL) and b.process(xyz0, EYE).segments == n
+    a.tracks_sync(all_tracks(n))                       # a: the tracks first, then the objects
+    oa = a.objects()
+    ob = b.objects()                                   # b: the other order
+    b.tracks_sync(all_tracks(n))
+    lists = a.label_indices()
+    assert len(set(len(l) for l in lists[1:])) >= 3
+    for l in range(1, n + 1):
+        np.testing.assert_array_equal(a.track_indices(100 + l), lists[l])
+        np.testing.assert_array_equal(b.track_indices(100 + l), lists[l])
+    assert len(oa) == len(ob) > 0
+    for f in S.OBJECT_DTYPE.names:
+        np.testing.assert_array_equal(oa[f], ob[f], err_msg=f)
+    for o in oa:
+        assert o["num_points"] == len(lists[o["id"]])
+    # a second, different scan, and only the tracks ask: the lists are this scan's
+    assert a.process(xyz1, EYE).segments == n
+    a.tracks_sync(all_tracks(n))
+    lists1 = a.label_indices()
+    assert any(len(lists1[l]) != len(lists[l]) for l in range(1, n + 1))
+    for l in range(1, n + 1):
+        np.testing.assert_array_equal(a.track_indices(100 + l), lists1[l])
+    # ... and the objects that follow them are those of a handle that saw this scan alone
+    b.process(xyz1, EYE)
+    oa1, ob1 = a.objects(), b.objects()
+    assert len(oa1) == len(ob1) > 0
+    for f in S.OBJECT_DTYPE.names:
+        np.testing.assert_array_equal(oa1[f], ob1[f], err_msg=f)
+    a.close()
+    b.close()
+
+
+@pytest.mark.parametrize("mode", ["host", "device"])
+def test_mode_switch_drops_the_scan(mode):
+    """After ddlo_seg_set_labelling to the other mode the handle holds no scan: what needs one is
+    GICP_EINVAL, and no track's list changes."""
+    H = 16
+    seg = S.Segmentation(0, synth_params(H), labelling=mode)
+    xyz, _ = synth_scan(H, SMALL, 21)
+    n = seg.process(xyz, EYE).segments
+    assert n == len(SMALL)
+    seg.tracks_sync(all_tracks(n))
+    held = {t: seg.track_indices(t).copy() for t, _ in all_tracks(n)}
+    assert len(set(len(v) for v in held.values())) >= 3
+    before = seg.tracks_stats()
+    seg.objects()
+    seg.classify([(101, 0)])
+    seg.labelling = "device" if mode == "host" else "host"
+    for call in (seg.objects, lambda: seg.tracks_sync([(300, 1)]), lambda: seg.static_cloud([1]),
+                 lambda: seg.static_cloud_tracks([101]), lambda: seg.classify([(101, 0)])):
+        with pytest.raises(P.GicpError) as e:
+            call()
+        assert e.value.status == 1                     # GICP_EINVAL
+    assert seg.tracks_stats() == before
+    for t, want in held.items():
+        np.testing.assert_array_equal(seg.track_indices(t), want)
+    # switching back does not bring the scan back; a new scan in the new mode does
+    seg.labelling = mode
+    with pytest.raises(P.GicpError):
+        seg.objects()
+    seg.labelling = "device" if mode == "host" else "host"
+    assert seg.process(xyz, EYE).segments == n
+    assert len(seg.objects()) > 0
+    seg.tracks_sync([(300, 1)])
+    np.testing.assert_array_equal(seg.track_indices(300), seg.label_indices()[1])
+    seg.close()
+
+
 # ---- the driver -----------------------------------------------------------------------------------
 def result_key(r):
     def g(x):
