@@ -220,6 +220,65 @@ __device__ __forceinline__ void resolve_tied_corr(const AlignJob* __restrict__ j
 #define DDLO_LOOKUP_U 16
 #endif
 constexpr int kLookupU = DDLO_LOOKUP_U;
+// Remainder phase of the fused lookup.  Every lane scans entries [0, kTailE0)
+// of its own list as above.  A wavefront in which H > 0 lanes then have
+// entries left (a ballot) shares them: the heavy lane of rank r (in lane
+// order) is served by the aligned team of F lanes r F .. r F + F - 1, F the
+// largest power of two with H F <= 64 (at most kTailFCap); member m scans the
+// kLookupU-entry chunks c = m (mod F) of [kTailE0, cnt) against the owner's
+// query, and the members' partial results are merged by a butterfly over the
+// team and moved back to the owner.  The merge (tail_merge) is the second
+// order statistic of a union of disjoint entry sets, which is what the
+// sequential scan computes, so key, second distance and coordinates are the
+// sequential scan's bit for bit whatever the partition.  H > 32: F = 1, every
+// lane goes on alone.  No LDS, no barrier; a wavefront without a long list
+// pays one ballot and one branch.  Measured (profiles/lookup_tail_summary.md):
+// kTailE0 16 and 48 and a cap of 8 on F slower, a cap of 16 the same; a member
+// that loads its next chunk before it consumes the current one more than
+// twice as slow (not kept).  (-DDDLO_TAIL_E0 / -DDDLO_TAIL_FCAP: A/B builds.)
+#ifndef DDLO_TAIL_E0
+#define DDLO_TAIL_E0 32
+#endif
+#ifndef DDLO_TAIL_FCAP
+#define DDLO_TAIL_FCAP 64
+#endif
+constexpr unsigned kTailE0 = DDLO_TAIL_E0;
+constexpr int kTailFCap = DDLO_TAIL_FCAP;
+static_assert(kTailE0 > 0 && kTailE0 % kLookupU == 0, "the common rounds end on a round boundary");
+static_assert(kTailFCap >= 1 && kTailFCap <= 64 && (kTailFCap & (kTailFCap - 1)) == 0, "team size: a power of two");
+
+// One lane's lookup result over the entries it has seen: the smallest
+// (distance, position) key with its point, and the smallest distance of any
+// other entry (the second order statistic: it feeds the tie test only).
+struct LookupBest {
+  unsigned long long bk;
+  float d2, bx, by, bz;
+};
+// a <- the result over the union of a's and o's (disjoint) entry sets
+__device__ __forceinline__ void tail_merge(LookupBest& a, const LookupBest& o, bool track2) {
+  const bool take = o.bk < a.bk;
+  const unsigned long long loser = take ? a.bk : o.bk;
+  if (take) {
+    a.bk = o.bk;
+    a.bx = o.bx;
+    a.by = o.by;
+    a.bz = o.bz;
+  }
+  if (track2) {
+    a.d2 = fminf(a.d2, o.d2);
+    if (loser != ~0ull) a.d2 = fminf(a.d2, __uint_as_float((unsigned)(loser >> 32)));
+  }
+}
+__device__ __forceinline__ LookupBest tail_shfl(const LookupBest& s, int src) {
+  LookupBest r;
+  r.bk = ((unsigned long long)(unsigned)__shfl((int)(unsigned)(s.bk >> 32), src) << 32) |
+         (unsigned)__shfl((int)(unsigned)s.bk, src);
+  r.d2 = __shfl(s.d2, src);
+  r.bx = __shfl(s.bx, src);
+  r.by = __shfl(s.by, src);
+  r.bz = __shfl(s.bz, src);
+  return r;
+}
 
 // developer build (-DDDLO_MOM_PROF): a wave timeline of the fused-lookup
 // moment kernel, s_memrealtime stamps (100 MHz, one clock for the device)
@@ -227,7 +286,8 @@ constexpr int kLookupU = DDLO_LOOKUP_U;
 #ifdef DDLO_MOM_PROF
 #define MOM_PROF(i) if (LOOKUP) mp_t[i] = __builtin_amdgcn_s_memrealtime()
 constexpr int kMomProfIters = 8, kMomProfWaves = 2048;
-__device__ unsigned long long g_mom_prof[kMomProfIters * kMomProfWaves * 6];   // [iteration][wave][stamp]
+constexpr int kMomProfWords = 7;   // six stamps, then the remainder phase's word: H | rounds << 8
+__device__ unsigned long long g_mom_prof[kMomProfIters * kMomProfWaves * kMomProfWords];   // [iteration][wave][word]
 #else
 #define MOM_PROF(i)
 #endif
@@ -317,7 +377,7 @@ template <bool FUSE_LM, bool LOOKUP = false>
 __global__ __launch_bounds__(64 * kMomWaves) void k_moments(const AlignJob* __restrict__ job,
                                                             AlignState* __restrict__ st, AlignState* __restrict__ publish) {
 #ifdef DDLO_MOM_PROF
-  unsigned long long mp_t[6] = {0, 0, 0, 0, 0, 0};
+  unsigned long long mp_t[kMomProfWords] = {0, 0, 0, 0, 0, 0, 0};
 #endif
   MOM_PROF(0);
   // st (= job->state) is a kernel argument and the pose is loaded with the
@@ -409,37 +469,87 @@ __global__ __launch_bounds__(64 * kMomWaves) void k_moments(const AlignJob* __re
           cg_cell_list(G, tx, ty, tz, off, cnt);   // (no fallback cell in LOOKUP mode)
         }
       }
-      unsigned long long bk = ~0ull;
-      float d2 = INFINITY, bx = 0.f, by = 0.f, bz = 0.f;
+      LookupBest own{~0ull, INFINITY, 0.f, 0.f, 0.f};
       const bool track2 = tie_detect;   // the second distance only feeds the tie test
       constexpr int kU = kLookupU;   // loads in flight
-      auto consume = [&](const float4 (&pp)[kU], unsigned k) {
+      // entries [k, k + kU) of the list (lo, n), against the query q, into r
+      auto consume = [&](const float4 (&pp)[kU], unsigned k, unsigned n, float qx, float qy, float qz, LookupBest& r) {
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
-          if (k + u < cnt) {
-            const float dd = dist2(lqx, lqy, lqz, pp[u].x, pp[u].y, pp[u].z);
+          if (k + u < n) {
+            const float dd = dist2(qx, qy, qz, pp[u].x, pp[u].y, pp[u].z);
             const unsigned long long kk = dkey(dd, __float_as_int(pp[u].w));
-            if (kk < bk) {
-              if (track2 && bk != ~0ull) d2 = fminf(d2, __uint_as_float((unsigned)(bk >> 32)));
-              bk = kk;
-              bx = pp[u].x;
-              by = pp[u].y;
-              bz = pp[u].z;
+            if (kk < r.bk) {
+              if (track2 && r.bk != ~0ull) r.d2 = fminf(r.d2, __uint_as_float((unsigned)(r.bk >> 32)));
+              r.bk = kk;
+              r.bx = pp[u].x;
+              r.by = pp[u].y;
+              r.bz = pp[u].z;
             } else if (track2) {
-              d2 = fminf(d2, dd);
+              r.d2 = fminf(r.d2, dd);
             }
           }
         }
       };
-      auto fetch = [&](float4 (&pp)[kU], unsigned k) {
+      auto fetch = [&](float4 (&pp)[kU], unsigned k, unsigned lo, unsigned n) {
 #pragma unroll
-        for (int u = 0; u < kU; ++u) pp[u] = ldg4(G.ent, off + min(k + u, cnt - 1));
+        for (int u = 0; u < kU; ++u) pp[u] = ldg4(G.ent, lo + min(k + u, n - 1));
       };
-      for (unsigned k = 0; k < cnt; k += kU) {
+      const unsigned c0 = min(cnt, kTailE0);
+      for (unsigned k = 0; k < c0; k += kU) {
         float4 pp[kU];
-        fetch(pp, k);
-        consume(pp, k);
+        fetch(pp, k, off, cnt);
+        consume(pp, k, cnt, lqx, lqy, lqz, own);
       }
+      // the remainder phase (kTailE0): lists longer than the common rounds
+      const bool heavy = cnt > kTailE0;
+      const unsigned long long rem = __ballot(heavy);
+      if (rem != 0ull) {
+        const int H = __popcll(rem);
+        int lf = 0;   // log2 of the team size
+        while ((H << (lf + 1)) <= 64 && (2 << lf) <= kTailFCap) ++lf;
+        const int F = 1 << lf;
+        const int rank = __popcll(rem & ((1ull << lane) - 1ull));   // a heavy lane's rank
+        // the lane this one serves: its own (F = 1), or the heavy lane whose rank is this lane's team
+        int owner = lane;
+        if (F > 1) {
+          const int team = lane >> lf;
+          owner = -1;   // (H F < 64: the teams from H on are idle)
+          int r = 0;
+          for (unsigned long long mm = rem; mm; mm &= mm - 1, ++r)
+            if (team == r) owner = __builtin_ctzll(mm);
+        }
+        const int osrc = owner < 0 ? lane : owner;
+        const unsigned ooff = (unsigned)__shfl((int)off, osrc);
+        const unsigned ocnt0 = (unsigned)__shfl((int)cnt, osrc);   // (every lane takes part: a lane left out reads as 0)
+        const unsigned ocnt = owner < 0 ? 0u : ocnt0;
+        const float oqx = __shfl(lqx, osrc), oqy = __shfl(lqy, osrc), oqz = __shfl(lqz, osrc);
+        LookupBest mine{~0ull, INFINITY, 0.f, 0.f, 0.f};
+        const unsigned stride = (unsigned)kU << lf;
+        unsigned k = kTailE0 + (unsigned)kU * (unsigned)(lane & (F - 1));
+#ifdef DDLO_MOM_PROF
+        int rounds = 0;
+#define MOM_PROF_ROUND ++rounds
+#else
+#define MOM_PROF_ROUND
+#endif
+        for (; k < ocnt; k += stride) {
+          float4 pp[kU];
+          fetch(pp, k, ooff, ocnt);
+          consume(pp, k, ocnt, oqx, oqy, oqz, mine);
+          MOM_PROF_ROUND;
+        }
+#undef MOM_PROF_ROUND
+        // the team's result in every member, then in the owner
+        for (int m = 1; m < F; m <<= 1) tail_merge(mine, tail_shfl(mine, lane ^ m), track2);
+        const LookupBest got = tail_shfl(mine, heavy && F > 1 ? rank << lf : lane);   // (F = 1: its own)
+        if (heavy) tail_merge(own, got, track2);
+#ifdef DDLO_MOM_PROF
+        mp_t[6] = (unsigned long long)H | ((unsigned long long)wave_max((float)rounds) << 8);
+#endif
+      }
+      const unsigned long long bk = own.bk;
+      const float d2 = own.d2, bx = own.bx, by = own.by, bz = own.bz;
       lkey = owned ? umin64(bk, dkey(job->cap2, -1)) : dkey(INFINITY, -1);
       const float lkd = __uint_as_float((unsigned)(lkey >> 32));
       lsec = (owned && (unsigned)lkey != 0xffffffffu && d2 == lkd) ? (unsigned)(lkey >> 32) : 0xffffffffu;
@@ -590,8 +700,8 @@ __global__ __launch_bounds__(64 * kMomWaves) void k_moments(const AlignJob* __re
 #ifdef DDLO_MOM_PROF
   MOM_PROF(5);
   if (LOOKUP && lane == 0 && wave < kMomProfWaves) {
-    unsigned long long* o = g_mom_prof + ((size_t)min(st->iter, kMomProfIters - 1) * kMomProfWaves + wave) * 6;
-    for (int e = 0; e < 6; ++e) o[e] = mp_t[e];
+    unsigned long long* o = g_mom_prof + ((size_t)min(st->iter, kMomProfIters - 1) * kMomProfWaves + wave) * kMomProfWords;
+    for (int e = 0; e < kMomProfWords; ++e) o[e] = mp_t[e];
   }
 #endif
   if constexpr (FUSE_LM) {
@@ -676,7 +786,7 @@ void launch_mom_reduce(hipStream_t s, const AlignJob* job) { k_mom_reduce<<<1, k
 }  // namespace ddlo
 
 #ifdef DDLO_MOM_PROF
-// developer build: the fused moment kernel's wave stamps of the last align, [iteration][wave][6]
+// developer build: the fused moment kernel's wave stamps of the last align, [iteration][wave][7]
 extern "C" int ddlo_dev_mom_prof(unsigned long long* out) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(ddlo::g_mom_prof), sizeof(ddlo::g_mom_prof));
 }
