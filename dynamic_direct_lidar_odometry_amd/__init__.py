@@ -215,9 +215,14 @@ def load():
         "gicp_set_target_grid": (I, [P, I]),
         "gicp_get_target_grid_info": (I, [P, C.POINTER(GicpGridInfo)]),
         "gicp_get_lookup_stats": (I, [P, C.POINTER(C.c_int64)]),
+        "gicp_get_start_counts": (I, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     }
     for name, (res, args) in sig.items():
-        f = getattr(L, name)
+        f = getattr(L, name, None)
+        if f is None and name == "gicp_get_start_counts" and "DDLO_GICP_LIB" in os.environ:
+            continue   # an A/B build of an earlier ABI (timing runs): Context.start_counts() is not available
+        if f is None:
+            raise AttributeError(f"{path}: no symbol {name}")
         f.restype = res
         f.argtypes = args
     _LIB = L
@@ -495,6 +500,13 @@ class Context:
         v = C.c_int64(0)
         self._check(self.L.gicp_get_lookup_stats(self.h, C.byref(v)))
         return int(v.value)
+
+    def start_counts(self):
+        """(fresh_starts, init_starts): aligns of this context started by the first iteration's kernel
+        itself / by the init kernel (gicp_get_start_counts)."""
+        f, i = C.c_int64(0), C.c_int64(0)
+        self._check(self.L.gicp_get_start_counts(self.h, C.byref(f), C.byref(i)))
+        return int(f.value), int(i.value)
 
     def set_tie_order(self, nanoflann_order=True):
         """Exact distance ties in nanoflann's traversal order (default) or by Morton position."""

@@ -545,7 +545,7 @@ struct JobCommit {
   explicit JobCommit(gicp_ctx* ctx) : c(ctx) {}
   void done() { ok = true; }
   ~JobCommit() {
-    if (!ok) c->job_last_valid = false;
+    if (!ok) c->job_last_valid = c->fresh_ok = false;
   }
 };
 
@@ -820,6 +820,34 @@ void drop_graphs(gicp_ctx* c) {
 // its graphs, has run.
 gicp_status graph_set(gicp_ctx* c, const std::array<long long, 7>& key, int nblocks, GraphSet** out);
 
+// DDLO_FRESH_START=0 (dev builds): every align starts with k_align_init (A/B).
+bool fresh_start_enabled() {
+  static const bool on = [] {
+    const char* v = dev_getenv("DDLO_FRESH_START");
+    return !(v && *v == '0');
+  }();
+  return on;
+}
+
+// An align may start without k_align_init when the device job and state are
+// provably what the init kernel would find and leave but for the words
+// k_moments_fresh writes itself:
+//   - the job is the device's copy but for the guess and the ticket
+//     (finalize_job left job_full = 0), so the state's src_radius holds too;
+//   - the linearize is the fused one-kernel lookup with the LM step in its
+//     last block, unsharded, with no profiling and no per-wave statistics;
+//   - at least one iteration runs;
+//   - prev_ok: the ctx's last align completed on the graph path without an
+//     error -- the state is a completed align's, the arrival word is re-armed
+//     -- and published tie words that were all 0 (no kernel can zero them at
+//     the start of a launch whose blocks add to them).
+bool fresh_start_allowed(const gicp_ctx* c, bool prev_ok, int max_it) {
+  if (!prev_ok || !fresh_start_enabled() || c->job_host->job_full != 0 || max_it <= 0) return false;
+  if (c->comm || c->profiling || c->stats_on) return false;
+  const LinGeom g = geometry(c);
+  return linearize_is_one_kernel(g) && g.fuse_lm;
+}
+
 // Launch the align as a first chunk of n outer iterations (n = the previous
 // align's iteration count on this ctx: aligns of consecutive scans converge
 // in similar counts) followed by single-iteration chunks, keeping one
@@ -828,7 +856,17 @@ gicp_status graph_set(gicp_ctx* c, const std::array<long long, 7>& key, int nblo
 // align needed more than its first chunk).  After convergence at most that
 // one no-op iteration (three early-exiting kernels) runs.  Returns the index
 // of the chunk after which the state is final.
-gicp_status run_align_graph(gicp_ctx* c, int max_it, int nblocks, int* final_chunk) {
+// fresh (fresh_start_allowed): the first chunk starts without k_align_init
+// and is not a graph.  Its first iteration is k_moments_fresh -- the guess,
+// the ticket and rec0 are its arguments, which the runtime pushes with the
+// dispatch -- and its other first - 1 iterations are launched one by one
+// behind it while it runs.  Of the three ways to deliver the arguments that
+// was the fastest (profiles/fresh_start_summary.md: a graph of the other
+// iterations behind the kernel, and one graph whose first node's arguments
+// are updated per launch, both cost a graph launch the plain launches do
+// not).  The chunk publishes to slot 0 as the graph it stands for, so slots,
+// events, speculation and the prediction are unchanged.
+gicp_status run_align_graph(gicp_ctx* c, int max_it, int nblocks, bool fresh, int* final_chunk) {
   const void* jd = c->job_dev.p;
   // key: whether RCCL is in the chunk, the job buffer and the launch geometry
   const LinGeom g = geometry(c);
@@ -849,10 +887,10 @@ gicp_status run_align_graph(gicp_ctx* c, int max_it, int nblocks, int* final_chu
       (void)hipGetLastError();
       if (!c->comm) return s;
       c->comm_graphs = false;  // RCCL refused stream capture: launch chunks eagerly
-      return run_align_graph(c, max_it, nblocks, final_chunk);
+      return run_align_graph(c, max_it, nblocks, fresh, final_chunk);
     }
   }
-  if (use_graph && !gs->first[first - 1].ge) {
+  if (use_graph && !fresh && !gs->first[first - 1].ge) {
     gicp_status s = capture_chunk(c, true, first, nblocks, 0, &gs->first[first - 1]);
     if (s) {
       drop_graphs(c);
@@ -862,6 +900,18 @@ gicp_status run_align_graph(gicp_ctx* c, int max_it, int nblocks, int* final_chu
   // chunk k publishes to slot k % 2 (chunk 0: the first-chunk graph, slot 0)
   auto launch_chunk = [&](int k) -> gicp_status {
     const bool is_first = k == 0;
+    if (is_first && fresh) {
+      const AlignJob& jh = *c->job_host;
+      FreshStart fs{};
+      std::memcpy(fs.R, jh.guess_R, sizeof(fs.R));
+      std::memcpy(fs.t, jh.guess_t, sizeof(fs.t));
+      fs.ticket = jh.ticket;
+      fs.job_w = c->job_dev.as<AlignJob>();
+      fs.rec0 = jh.reuse && jh.reuse_rec0;
+      launch_linearize_fresh(c->stream, c->job_dev.as<AlignJob>(), g, fs, first == 1 ? c->state_host_dev : nullptr);
+      HIP_TRY(hipGetLastError());
+      return first > 1 ? enqueue_chunk(c, false, first - 1, nblocks, 0) : GICP_OK;
+    }
     if (use_graph) {
       HIP_TRY(hipGraphLaunch(is_first ? gs->first[first - 1].ge : gs->rest[k & 1].ge, c->stream));
       return GICP_OK;
@@ -1289,6 +1339,10 @@ gicp_status gicp_share_source(gicp_ctx* dst, const gicp_ctx* src) {
 
 gicp_status gicp_align(gicp_ctx* c, const float* guess16, float* out16, gicp_result* res) {
   if (!c) return fail(GICP_EINVAL, "null ctx");
+  // (cleared while the align is under way: an error return leaves it cleared)
+  bool prev_ok = c->fresh_ok;
+  c->fresh_ok = false;
+  bool graph_path = false;
   begin_ties(c);
   gicp_status s = set_device(c);
   if (s) return s;
@@ -1306,6 +1360,9 @@ gicp_status gicp_align(gicp_ctx* c, const float* guess16, float* out16, gicp_res
     finalize_job(c);
     JobCommit commit(c);
     const int max_it = c->job_host->max_iterations;
+    const bool fresh = fresh_start_allowed(c, prev_ok, max_it);
+    prev_ok = false;   // (a tie re-run changes the job: k_align_init)
+    ++(fresh ? c->fresh_aligns : c->init_aligns);
     end_ev = c->ev1;
     if (c->profiling) HIP_TRY(hipEventRecord(c->ev0, c->stream));   // (read only by the profiled path below)
     if (c->profiling || max_it <= 0) {
@@ -1319,11 +1376,13 @@ gicp_status gicp_align(gicp_ctx* c, const float* guess16, float* out16, gicp_res
       HIP_TRY(hipStreamSynchronize(c->stream));
       c->state_slot = 0;
       c->tail_pending = false;
+      graph_path = false;
     } else {
       int fc = 0;
-      s = run_align_graph(c, max_it, nblocks, &fc);
+      s = run_align_graph(c, max_it, nblocks, fresh, &fc);
       if (s) return s;
       commit.done();
+      graph_path = true;
       // chunk fc's end-of-chunk copy already put the final state in its
       // slot; the (at most one) speculative no-op chunk still queued writes
       // the other slot and does not delay the return
@@ -1383,6 +1442,9 @@ gicp_status gicp_align(gicp_ctx* c, const float* guess16, float* out16, gicp_res
     return fail(GICP_EHIP, "nanoflann tie order: a tied correspondence could not be re-run (bits " +
                                std::to_string(st.tie_err) + (st.tie_pending ? ", no tree" : "") + ")");
   if (st.lm_failed) g_last_error = "lm not converged!!";
+  // the next align may start without k_align_init (fresh_start_allowed): the state this one
+  // published holds every tie the align met, and a queued no-op chunk adds none
+  c->fresh_ok = graph_path && !st.tie_pending && !st.ties_resolved && !st.tie_err;
   return GICP_OK;
 }
 
@@ -1488,6 +1550,7 @@ gicp_status gicp_transform_source(gicp_ctx* c, float* out_xyz, size_t n, size_t 
 
 gicp_status gicp_linearize(gicp_ctx* c, const double* pose16, double* H36, double* b6, double* cost, int32_t* ncorr) {
   if (!c || !pose16) return fail(GICP_EINVAL, "null argument");
+  c->fresh_ok = false;   // (not an align on the graph path)
   begin_ties(c);
   gicp_status s = set_device(c);
   if (s) return s;
@@ -1686,6 +1749,13 @@ gicp_status gicp_get_target_grid_info(gicp_ctx* c, gicp_grid_info* out) {
   if (!c->tgt.cloud || !c->tgt.cloud->grid) return GICP_OK;
   *out = c->tgt.cloud->grid->info;
   out->built = grid_active(c) ? 1 : 0;
+  return GICP_OK;
+}
+
+gicp_status gicp_get_start_counts(gicp_ctx* c, int64_t* fresh_starts, int64_t* init_starts) {
+  if (!c) return fail(GICP_EINVAL, "null ctx");
+  if (fresh_starts) *fresh_starts = c->fresh_aligns;
+  if (init_starts) *init_starts = c->init_aligns;
   return GICP_OK;
 }
 

@@ -282,6 +282,19 @@ struct AlignJob {
 };
 constexpr int kFbSegs = 8;       // walk-list segments (a wavefront appends to segment wave % kFbSegs)
 
+// What k_align_init carries from the host to the device for an align whose
+// job is otherwise the previous one's (AlignJob::job_full = 0), as a by-value
+// kernel argument of k_moments_fresh: the runtime pushes kernel arguments with
+// the dispatch, so such an align needs no init kernel in front of its first
+// iteration (DESIGN.md §4 "Launch structure").
+struct FreshStart {
+  double R[9];                 // the guess (AlignJob::guess_R, guess_t)
+  double t[3];
+  unsigned long long ticket;   // AlignJob::ticket
+  AlignJob* job_w;             // the device job: block 0 stores its guess, job_full = 0 and ticket words
+  int rec0;                    // reuse && reuse_rec0: the first iteration records references
+};
+
 constexpr int kNfMaxLevels = 40;   // big levels of the device build (deeper: the build reports a failure)
 constexpr int kNfLevelSpare = 2;   // big levels a ctx's build carries beyond those its last build used
 

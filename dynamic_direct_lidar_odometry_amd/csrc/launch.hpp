@@ -63,6 +63,12 @@ bool lm_fusion_enabled(bool lookup);   // unsharded aligns on the one-kernel loo
 LinGeom linearize_geometry(int nsrc, int tgt_upper);
 // publish: with g.fuse_lm, the host-mapped state slot the fused LM step publishes to (or nullptr)
 void launch_linearize(hipStream_t s, const AlignJob* job, const LinGeom& g, AlignState* publish = nullptr);
+bool linearize_is_one_kernel(const LinGeom& g);   // every query is answered by its cell: the lookup runs in k_moments
+// An align's first iteration without k_align_init in front of it (k_moments_fresh): only where
+// linearize_is_one_kernel(g) && g.fuse_lm, for a device job that is this align's but for the guess and
+// the ticket and a state whose tie words are 0.
+void launch_linearize_fresh(hipStream_t s, const AlignJob* job, const LinGeom& g, const FreshStart& fs,
+                            AlignState* publish = nullptr);
 int search_queries_per_wave();
 int task_cap_per_region(int nsrc);   // task-list slots per region for nsrc source points
 int moment_blocks(int nsrc);  // slab rows written by the moment kernel

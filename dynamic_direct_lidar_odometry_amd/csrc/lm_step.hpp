@@ -295,10 +295,16 @@ __device__ __forceinline__ void reduce_slab(const double* slab_in, int nb, doubl
 // st, slab, nblocks: job->state, job->slab, job->nblocks, passed as kernel
 // arguments so the slab loads need no job load first; premom (PREMOM): the
 // moments already reduced (and summed across shards: job->mom).
-template <bool PREMOM>
+// FRESH (k_moments_fresh, an align's first step without k_align_init before
+// it): the state still holds the previous align's words, so the step starts
+// from the values the init kernel would have stored (iteration 0, no trials,
+// lambda -1, the guess and rec0 from fs) and stores every word the init
+// kernel resets whether this step sets it or not; the state it leaves is the
+// one k_align_init + the plain step leave, word for word.
+template <bool PREMOM, bool FRESH = false>
 __device__ __forceinline__ void lm_step_body(const AlignJob* __restrict__ job, AlignState* __restrict__ st,
                                              const double* __restrict__ slab, int nblocks,
-                                             const double* __restrict__ premom) {
+                                             const double* __restrict__ premom, const FreshStart* fs = nullptr) {
 #ifdef DDLO_LM_PROF
   unsigned long long lm_t[6], lm_tt[4] = {0, 0, 0, 0};
 #endif
@@ -317,15 +323,21 @@ __device__ __forceinline__ void lm_step_body(const AlignJob* __restrict__ job, A
   __shared__ int tr_conv[kMaxTrials];
   const int tid = threadIdx.x;
   // state words, loaded before the slab (their latency overlaps it)
-  const int it_pre = st->iter;
-  const int trials_pre = st->lm_trials;
-  const int rec_pre = st->rec;
-  const float src_radius = st->src_radius;
-  const double lambda_pre = st->lambda;
+  const int it_pre = FRESH ? 0 : st->iter;
+  const int trials_pre = FRESH ? 0 : st->lm_trials;
+  const int rec_pre = FRESH ? fs->rec0 : st->rec;
+  const float src_radius = st->src_radius;   // (FRESH too: only a whole job changes it)
+  const double lambda_pre = FRESH ? -1.0 : st->lambda;
   // the pose, held in a register until the slab loads are issued (an LDS
   // store here would wait for it first)
   double rt_v = 0.0;
-  if (tid < 12) rt_v = tid < 9 ? st->R[tid] : st->t[tid - 9];
+  if constexpr (FRESH) {   // the guess: kernel arguments (scalar registers), one select per entry
+#pragma unroll
+    for (int e = 0; e < 12; ++e)
+      if (tid == e) rt_v = e < 9 ? fs->R[e] : fs->t[e - 9];
+  } else {
+    if (tid < 12) rt_v = tid < 9 ? st->R[tid] : st->t[tid - 9];
+  }
   // job words and this thread's table entry too (misses at their first use would each stall a phase)
   const int optimizer = job->optimizer, lm_max_iterations = job->lm_max_iterations;
   const int fixed_iterations = job->fixed_iterations, max_iterations = job->max_iterations;
@@ -459,24 +471,37 @@ __device__ __forceinline__ void lm_step_body(const AlignJob* __restrict__ job, A
         st->lambda = tr_lambda[ntr - 1] * 2.0;  // not observable: the align ends
       }
     }
+  } else if (FRESH && lane == 0) {   // GN leaves both as k_align_init set them
+    st->lm_trials = 0;
+    st->lambda = -1.0;
   }
   if (lane == 0) {
     st->nr_iterations = it_pre;
     st->final_cost = mom[kMomY0];
     st->num_corr = (int)mom[kMomCount];
     if (rec_pre) st->any_rec = 1;   // this iteration's search recorded references
+    else if (FRESH) st->any_rec = 0;
     st->iter = it_pre + 1;
     st->have_prev = 1;
     int done = 0;
-    if (!ok) {
-      st->lm_failed = 1;
-      done = 1;
-    } else if (tr_conv[chosen]) {
-      st->converged = 1;
-      done = 1;
+    if constexpr (FRESH) {
+      const int failed = !ok, conv = ok && tr_conv[chosen];
+      st->lm_failed = failed;
+      st->converged = conv;
+      done = failed | conv;
+      if (it_pre + 1 >= max_iterations) done = 1;
+      st->done = done;
+    } else {
+      if (!ok) {
+        st->lm_failed = 1;
+        done = 1;
+      } else if (tr_conv[chosen]) {
+        st->converged = 1;
+        done = 1;
+      }
+      if (it_pre + 1 >= max_iterations) done = 1;
+      if (done) st->done = 1;
     }
-    if (it_pre + 1 >= max_iterations) done = 1;
-    if (done) st->done = 1;
   }
   // accepted: x0 = delta * x0 (compose, lsq_registration_impl.hpp:193-197,225-228),
   // one entry of (Rn | tn) per lane
@@ -494,6 +519,9 @@ __device__ __forceinline__ void lm_step_body(const AlignJob* __restrict__ job, A
     } else if (lane >= 16 && lane < 16 + 36) {
       st->final_hessian[lane - 16] = Hs[lane - 16];
     }
+  } else if (FRESH && lane < 12) {   // not accepted: the pose stays the guess (final_hessian: no kernel resets it)
+    if (lane < 9) st->R[lane] = Rt_s[lane];
+    else st->t[lane - 9] = Rt_s[lane];
   }
   int rec = reuse;
   if (accept) {

@@ -328,8 +328,11 @@ __device__ __forceinline__ TieWords fetch_tie_words(AlignState* st) {
 //   3. every storing wave drains its pinned stores, one barrier;
 //   4. thread 0's system-scope release store of the word, ordered behind the
 //      barrier, covers the block's stores.
+// ticket: the align's ticket where the device job does not hold it yet
+// (k_moments_fresh stores it in this same launch), else nullptr.
 __device__ __forceinline__ void publish_state(const AlignJob* __restrict__ job, AlignState* __restrict__ st,
-                                              AlignState* __restrict__ publish, const TieWords& tw) {
+                                              AlignState* __restrict__ publish, const TieWords& tw,
+                                              const unsigned long long* ticket = nullptr) {
   static_assert(sizeof(AlignState) % 8 == 0, "AlignState is copied in 8-byte words");
   static_assert(offsetof(AlignState, pub) == sizeof(AlignState) - 8, "the publication word is the last 8 bytes");
   static_assert(offsetof(AlignState, iter) % 8 == 0 && offsetof(AlignState, done) == offsetof(AlignState, iter) + 4,
@@ -363,7 +366,7 @@ __device__ __forceinline__ void publish_state(const AlignJob* __restrict__ job, 
     dst[w] = v;
     if (w == (int)(offsetof(AlignState, iter) / 8)) iter_s = v;
   }
-  const unsigned long long tk = job->ticket;
+  const unsigned long long tk = ticket ? *ticket : job->ticket;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -373,30 +376,65 @@ __device__ __forceinline__ void publish_state(const AlignJob* __restrict__ job, 
   }
 }
 
-template <bool FUSE_LM, bool LOOKUP = false>
-__global__ __launch_bounds__(64 * kMomWaves) void k_moments(const AlignJob* __restrict__ job,
-                                                            AlignState* __restrict__ st, AlignState* __restrict__ publish) {
+// FRESH (k_moments_fresh, below): the first iteration of an align whose job is
+// the previous align's but for the guess and the ticket, with no k_align_init
+// in front of it.  The state still holds the previous align's words (done
+// set), so nothing of it is read at the start: the pose is the guess in fs
+// (kernel arguments: uniform, in scalar registers, no load), rec is fs->rec0
+// and no earlier iteration recorded; block 0 stores the device job's header
+// words and zeroes the walk list's total as the init kernel does, and the
+// last block's LM step and publication take their start values and the
+// ticket from fs (lm_step_body<.., FRESH>).  What only the host can
+// guarantee is its rule for this form (run_align_graph): the three tie words
+// are 0 -- any block may add to them in this launch, so no block can reset
+// them -- and the arrival word is 0, as every completed fused launch leaves it.
+template <bool FUSE_LM, bool LOOKUP, bool FRESH>
+__device__ __forceinline__ void moments_body(const AlignJob* __restrict__ job, AlignState* __restrict__ st,
+                                             AlignState* __restrict__ publish, const FreshStart* fs) {
+  static_assert(!FRESH || (FUSE_LM && LOOKUP), "the fresh start exists for the fused one-kernel lookup iteration only");
 #ifdef DDLO_MOM_PROF
   unsigned long long mp_t[kMomProfWords] = {0, 0, 0, 0, 0, 0, 0};
 #endif
   MOM_PROF(0);
-  // st (= job->state) is a kernel argument and the pose is loaded with the
-  // done flag, before the test: the state words are one load from the
-  // arguments, not three dependent ones (job -> state -> done -> pose)
-  const auto sg = gp(st);
   double R[9], t[3];
-  for (int e = 0; e < 9; ++e) R[e] = sg->R[e];
-  for (int e = 0; e < 3; ++e) t[e] = sg->t[e];
-  const int st_rec = sg->rec, st_any_rec = sg->any_rec;
-  if (__builtin_amdgcn_readfirstlane(sg->done)) {
-    // a no-op iteration after convergence: the chunk's publication still
-    // happens (as k_lm_step's after an early exit), by block 0
-    if (FUSE_LM && publish && blockIdx.x == 0) {
-      TieWords tw{};
-      if (threadIdx.x == kTieThread) tw = fetch_tie_words(st);
-      publish_state(job, st, publish, tw);
+  int st_rec, st_any_rec;
+  if constexpr (FRESH) {
+    for (int e = 0; e < 9; ++e) R[e] = fs->R[e];
+    for (int e = 0; e < 3; ++e) t[e] = fs->t[e];
+    st_rec = fs->rec0;
+    st_any_rec = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 64) {
+      // the words k_align_init copies for such an align: the later kernels of
+      // the align read the ticket (publish_state) behind a kernel boundary
+      static_assert(offsetof(AlignJob, guess_t) == offsetof(AlignJob, guess_R) + 72 &&
+                        offsetof(AlignJob, job_full) == offsetof(AlignJob, guess_R) + 96 &&
+                        offsetof(AlignJob, ticket) == offsetof(AlignJob, guess_R) + 104,
+                    "guess_R, guess_t, job_full, ticket: the job's 14 header words");
+      AlignJob* const jw = fs->job_w;
+      for (int e = 0; e < 9; ++e) jw->guess_R[e] = fs->R[e];
+      for (int e = 0; e < 3; ++e) jw->guess_t[e] = fs->t[e];
+      jw->job_full = 0;
+      jw->ticket = fs->ticket;
     }
-    return;
+  } else {
+    // st (= job->state) is a kernel argument and the pose is loaded with the
+    // done flag, before the test: the state words are one load from the
+    // arguments, not three dependent ones (job -> state -> done -> pose)
+    const auto sg = gp(st);
+    for (int e = 0; e < 9; ++e) R[e] = sg->R[e];
+    for (int e = 0; e < 3; ++e) t[e] = sg->t[e];
+    st_rec = sg->rec;
+    st_any_rec = sg->any_rec;
+    if (__builtin_amdgcn_readfirstlane(sg->done)) {
+      // a no-op iteration after convergence: the chunk's publication still
+      // happens (as k_lm_step's after an early exit), by block 0
+      if (FUSE_LM && publish && blockIdx.x == 0) {
+        TieWords tw{};
+        if (threadIdx.x == kTieThread) tw = fetch_tie_words(st);
+        publish_state(job, st, publish, tw);
+      }
+      return;
+    }
   }
   const CloudDev src = job->src;
   const CloudDev tgt = job->tgt;
@@ -427,7 +465,8 @@ __global__ __launch_bounds__(64 * kMomWaves) void k_moments(const AlignJob* __re
   if (blockIdx.x == 0 && job->grid_on && threadIdx.x == 0) {   // the walk list is consumed: its total, then reset
     unsigned t = 0;
     for (int sg = 0; sg < kFbSegs; ++sg) t += job->fb_count[sg * 32];
-    job->fb_count[kFbSegs * 32] += t;
+    if constexpr (FRESH) job->fb_count[kFbSegs * 32] = 0u;   // the align's first iteration (no walk in front of it)
+    else job->fb_count[kFbSegs * 32] += t;
     for (int sg = 0; sg < kFbSegs; ++sg) job->fb_count[sg * 32] = 0u;
   }
   double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;
@@ -715,15 +754,29 @@ __global__ __launch_bounds__(64 * kMomWaves) void k_moments(const AlignJob* __re
     if (threadIdx.x == 0) {
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      atomicExch(arrive, 0u);   // re-armed for the next iteration (k_align_init zeroes it per align)
+      // re-armed for the next iteration, and for the next align's when that starts without
+      // k_align_init, which zeroes it per align
+      atomicExch(arrive, 0u);
     }
     __syncthreads();
     // every block has arrived, so the tie words are final: fetched in flight with the slab loads
     TieWords tw{};
     if (publish && threadIdx.x == kTieThread) tw = fetch_tie_words(st);
-    lm_step_body<false>(job, st, job->slab, job->nblocks, nullptr);
-    if (publish) publish_state(job, st, publish, tw);
+    lm_step_body<false, FRESH>(job, st, job->slab, job->nblocks, nullptr, fs);
+    if (publish) publish_state(job, st, publish, tw, FRESH ? &fs->ticket : nullptr);
   }
+}
+
+template <bool FUSE_LM, bool LOOKUP = false>
+__global__ __launch_bounds__(64 * kMomWaves) void k_moments(const AlignJob* __restrict__ job,
+                                                            AlignState* __restrict__ st, AlignState* __restrict__ publish) {
+  moments_body<FUSE_LM, LOOKUP, false>(job, st, publish, nullptr);
+}
+// The fused lookup iteration as an align's first kernel (moments_body<.., FRESH>).
+__global__ __launch_bounds__(64 * kMomWaves) void k_moments_fresh(const AlignJob* __restrict__ job,
+                                                                  AlignState* __restrict__ st,
+                                                                  AlignState* __restrict__ publish, const FreshStart fs) {
+  moments_body<true, true, true>(job, st, publish, &fs);
 }
 template __global__ void k_moments<false>(const AlignJob*, AlignState*, AlignState*);
 template __global__ void k_moments<true>(const AlignJob*, AlignState*, AlignState*);
@@ -758,9 +811,12 @@ __global__ __launch_bounds__(kLmThreads) void k_lm_step(const AlignJob* __restri
   if (publish) publish_state(job, st, publish, tw);
 }
 
-void launch_linearize(hipStream_t s, const AlignJob* job, const LinGeom& g, AlignState* publish) {
+bool linearize_is_one_kernel(const LinGeom& g) {
   static const int fused_lookup = env_knob("DDLO_GRID_FUSED", 1);   // 0: separate lookup kernel (A/B)
-  if (g.grid && !g.grid_walk && fused_lookup) {
+  return g.grid && !g.grid_walk && fused_lookup;
+}
+void launch_linearize(hipStream_t s, const AlignJob* job, const LinGeom& g, AlignState* publish) {
+  if (linearize_is_one_kernel(g)) {
     // every query is answered by its cell: the lookup runs inside the moment kernel
     if (g.fuse_lm) k_moments<true, true><<<g.mom_blocks, 64 * kMomWaves, 0, s>>>(job, g.state, publish);
     else k_moments<false, true><<<g.mom_blocks, 64 * kMomWaves, 0, s>>>(job, g.state, nullptr);
@@ -771,6 +827,11 @@ void launch_linearize(hipStream_t s, const AlignJob* job, const LinGeom& g, Alig
   if (!g.grid || g.grid_walk) launch_nn_walk(s, job, g);
   if (g.fuse_lm) k_moments<true><<<g.mom_blocks, 64 * kMomWaves, 0, s>>>(job, g.state, publish);
   else k_moments<false><<<g.mom_blocks, 64 * kMomWaves, 0, s>>>(job, g.state, nullptr);
+}
+void launch_linearize_fresh(hipStream_t s, const AlignJob* job, const LinGeom& g, const FreshStart& fs,
+                            AlignState* publish) {
+  // (the caller has checked the geometry: linearize_is_one_kernel(g) && g.fuse_lm)
+  k_moments_fresh<<<g.mom_blocks, 64 * kMomWaves, 0, s>>>(job, g.state, publish, fs);
 }
 int moment_blocks(int nsrc) {
   const int groups = (nsrc + 63) / 64;

@@ -375,6 +375,12 @@ struct gicp_ctx {
   AlignJob* job_host = nullptr;   // pinned
   AlignJob job_last{};            // the job k_align_init last copied whole (AlignJob::job_full)
   bool job_last_valid = false;
+  // The next align may start without k_align_init (run_align_graph, k_moments_fresh): the last align
+  // on this ctx completed on the graph path without an error and published tie words that are all 0.
+  // Cleared with job_last_valid, by every other route that writes the device state and while an
+  // align is under way (so an error return leaves it cleared).
+  bool fresh_ok = false;
+  long long fresh_aligns = 0, init_aligns = 0;   // aligns started by k_moments_fresh / by k_align_init (gicp_get_start_counts)
   AlignJob* job_host_dev = nullptr;     // its device-side address (read by k_align_init)
   AlignState* state_host_dev = nullptr; // state_host's device-side address (written by k_lm_step)
   // pinned, two slots: chunk k publishes its end state to slot k % 2, so the
@@ -1030,6 +1036,7 @@ inline gicp_status compute_cov(gicp_ctx* c, Side& side, int k_use = 0) {
 inline void invalidate_align(gicp_ctx* c) {
   c->have_align = false;
   c->job_last_valid = false;
+  c->fresh_ok = false;
 }
 
 }  // namespace rt

@@ -281,6 +281,13 @@ gicp_status gicp_get_target_grid_info(struct gicp_ctx* ctx, gicp_grid_info* out)
 /* Queries the last align's final linearize answered from the candidate cells
  * and sub-groups of 16 it left to the walk (diagnostics). */
 gicp_status gicp_get_lookup_stats(struct gicp_ctx* ctx, int64_t* walk_groups);
+/* How this ctx's aligns were started, counted since its creation (diagnostics,
+ * tests): fresh_starts by the first iteration's kernel itself, its guess in
+ * the kernel arguments (an align whose job is the previous align's but for
+ * the guess, on the fused candidate-cell path, after an align that ended
+ * cleanly without ties); init_starts by the init kernel (every other align;
+ * an align run again for a tie counts twice).  Either pointer may be NULL. */
+gicp_status gicp_get_start_counts(struct gicp_ctx* ctx, int64_t* fresh_starts, int64_t* init_starts);
 
 /* nanoflann's kd-tree of a side's cloud as the device built it (tests):
  * vind[n]; per node (c1, c2, divfeat, parent) with divfeat -1 for a leaf

@@ -3,7 +3,8 @@
 usage: python tools/profile_summary.py <rocprof dir> [prefix=run] > profiles/<name>.md
 
 Besides rocprof's own per-kernel stats it splits every align() into its outer
-iterations (k_align_init, then per iteration the search kernels — k_cell_lookup,
+iterations (k_align_init, or k_moments_fresh -- the first iteration of an
+align that starts without the init kernel -- then per iteration the search kernels — k_cell_lookup,
 k_nn_seed + k_nn_scan, or none when the candidate-cell lookup is fused into
 k_moments — k_moments, k_mom_reduce + RCCL's all-reduce (sharded) and
 k_lm_step) and separates ACTIVE iterations from no-op launches (an
@@ -56,10 +57,15 @@ def main():
     SKIP = ("ncclDevKernel", "ncclKernel", "__amd_rocclr")
     aligns = []
     cur = None
+    fresh_aligns = 0
     for n, us in seq:
         if n == "k_align_init":
             cur = []
             aligns.append(cur)
+        elif n == "k_moments_fresh":   # starts an align and is its first (fused) iteration
+            cur = [("k_moments_fused", us)]
+            aligns.append(cur)
+            fresh_aligns += 1
         elif cur is not None and n in LOOP:
             cur.append((n, us))
         elif cur is not None and n.startswith(SKIP):
@@ -130,7 +136,8 @@ def main():
     print(f"- no-op iteration (3 launches) average: {avg(noop + noop_eager):.1f} us")
     if active_fused:
         print(f"\n## Graph aligns: the LM step fused into the lookup moment kernel ({len(active_fused)} active "
-              f"iterations)\n")
+              f"iterations; {fresh_aligns} of the {len(aligns)} aligns started by k_moments_fresh, whose time is "
+              f"their iteration 0)\n")
         print("| iteration | n | k_moments<true, true> us (lookup + moments + fan-in + LM step) |")
         print("|---:|---:|---:|")
         for it in sorted(fused_pos):
