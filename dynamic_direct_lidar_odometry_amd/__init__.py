@@ -186,6 +186,9 @@ def load():
         "gicp_knn_target": (I, [P, P, S, S, I, P, P]),
         "gicp_get_moments": (I, [P, P]),
         "gicp_debug_lm_step": (I, [P, C.POINTER(GicpLmState), P, I, P, C.POINTER(GicpLmState)]),
+        "gicp_debug_search_begin": (I, [P]),
+        "gicp_debug_search_step": (I, [P, P, I, P, P, P, P]),
+        "gicp_debug_search_state": (I, [P, P, P, P, P, P, P, P, S]),
         "gicp_set_profiling": (I, [P, I]),
         "gicp_debug_stats": (I, [P, I, P, S, C.POINTER(S)]),
         "gicp_get_stream": (I, [P, C.POINTER(P)]),
@@ -478,6 +481,33 @@ class Context:
                                               0 if slab is None else len(slab), None if mom is None else _ptr(mom),
                                               C.byref(out)))
         return out
+
+    def search_begin(self):
+        """Start a scripted sequence of search steps (gicp_debug_search_begin; tests)."""
+        self._check(self.L.gicp_debug_search_begin(self.h))
+
+    def search_step(self, pose, rec):
+        """One outer iteration at `pose` on the state the previous step left, recording reuse
+        references iff rec (gicp_debug_search_step; tests): (H, b, cost, matched count)."""
+        pose = np.ascontiguousarray(pose, np.float64)
+        H = np.zeros((6, 6)); b = np.zeros(6); cost = C.c_double(); nc = C.c_int32()
+        self._check(self.L.gicp_debug_search_step(self.h, _ptr(pose), int(bool(rec)), _ptr(H), _ptr(b), C.byref(cost),
+                                                  C.byref(nc)))
+        return H, b, cost.value, nc.value
+
+    def search_state(self) -> dict:
+        """The last iteration's per-query search state in the caller's order (gicp_debug_search_state):
+        corr, sqd (+inf: nothing found), sec (uint32; all ones: not searched), ref (n, 4) = (q_ref, B^2),
+        ref_p (n, 3) and ref_j (original target index of p1, -1: none), wr (the walk radius), any_rec (the
+        state's flag: the search reads the raw ref / ref_p only when it is set)."""
+        n = self.size(SOURCE)
+        corr, sqd, sec = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros(n, np.uint32)
+        ref, refp, wr = np.zeros((n, 4), np.float32), np.zeros((n, 4), np.float32), np.zeros(n, np.float32)
+        any_rec = C.c_int32()
+        self._check(self.L.gicp_debug_search_state(self.h, _ptr(corr), _ptr(sqd), _ptr(sec), _ptr(ref), _ptr(refp),
+                                                   _ptr(wr), C.byref(any_rec), n))
+        return dict(corr=corr, sqd=sqd, sec=sec, ref=ref, ref_p=refp[:, :3].copy(),
+                    ref_j=refp[:, 3].copy().view(np.int32), wr=wr, any_rec=int(any_rec.value))
 
     def knn_target(self, queries, k):
         q, stride = _xyz(queries)

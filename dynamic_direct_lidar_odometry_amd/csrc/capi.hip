@@ -1342,6 +1342,7 @@ gicp_status gicp_align(gicp_ctx* c, const float* guess16, float* out16, gicp_res
   // (cleared while the align is under way: an error return leaves it cleared)
   bool prev_ok = c->fresh_ok;
   c->fresh_ok = false;
+  c->dbg_search = false;
   bool graph_path = false;
   begin_ties(c);
   gicp_status s = set_device(c);
@@ -1551,6 +1552,7 @@ gicp_status gicp_transform_source(gicp_ctx* c, float* out_xyz, size_t n, size_t 
 gicp_status gicp_linearize(gicp_ctx* c, const double* pose16, double* H36, double* b6, double* cost, int32_t* ncorr) {
   if (!c || !pose16) return fail(GICP_EINVAL, "null argument");
   c->fresh_ok = false;   // (not an align on the graph path)
+  c->dbg_search = false;
   begin_ties(c);
   gicp_status s = set_device(c);
   if (s) return s;
@@ -1599,6 +1601,207 @@ gicp_status gicp_linearize(gicp_ctx* c, const double* pose16, double* H36, doubl
   if (b6) std::memcpy(b6, st.last_b, sizeof(double) * 6);
   c->have_align = true;
   c->last_nsrc = ns;
+  return GICP_OK;
+}
+
+// The search pose by pose (tests): gicp_linearize's start, then one iteration
+// per gicp_debug_search_step at the caller's pose and recording flag, on the
+// state the previous one left.
+gicp_status gicp_debug_search_begin(gicp_ctx* c) {
+  if (!c) return fail(GICP_EINVAL, "null ctx");
+  c->fresh_ok = false;   // (not an align on the graph path)
+  c->dbg_search = false;
+  begin_ties(c);
+  gicp_status s = set_device(c);
+  if (s) return s;
+  s = maybe_build_grid(c);
+  if (s) return s;
+  s = prepare_align(c);
+  if (s) return s;
+  const int ns = c->src.cloud->n;
+  s = fill_job(c, nullptr, linearize_blocks(ns));
+  if (s) return s;
+  c->job_host->optimizer = GICP_OPT_GAUSS_NEWTON;
+  c->job_host->max_iterations = 1 << 30;     // never reached: no step ends the sequence
+  c->job_host->fixed_iterations = 1 << 30;   // (and no step converges)
+  c->job_last_valid = false;                 // the whole job, and the next align's too (the steps patch the device job)
+  finalize_job(c);
+  JobCommit commit(c);   // not completed: the device job is never taken for an align's
+  launch_align_init(c->stream, c->job_dev.as<AlignJob>(), c->job_host_dev);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(c->state_host, c->state_dev.p, sizeof(AlignState), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->state_slot = 0;
+  c->tail_pending = false;
+  c->have_align = false;   // no linearization yet
+  c->last_nsrc = ns;
+  std::memcpy(&c->dbg_job, c->job_host, sizeof(AlignJob));
+  c->dbg_search = true;
+  return GICP_OK;
+}
+
+// The ctx would still build the job gicp_debug_search_begin sent: same clouds,
+// covariances, buffers, parameters, shard, tie tree and candidate cells.  A
+// setter called since (gicp_set_covariances, gicp_set_params, ...) makes the
+// device job stale; the step then refuses instead of running on it.
+static gicp_status debug_search_job_current(gicp_ctx* c) {
+  if (!c->src.cloud || !c->tgt.cloud || !c->src.has_cov() || !c->tgt.has_cov() || c->src.cloud->n != c->last_nsrc)
+    return fail(GICP_ESTATE, "the clouds or covariances changed since gicp_debug_search_begin");
+  const unsigned long long ticket = c->ticket;
+  gicp_status s = fill_job(c, nullptr, linearize_blocks(c->src.cloud->n));
+  c->ticket = ticket;
+  if (s) return s;
+  AlignJob& j = *c->job_host;
+  j.optimizer = c->dbg_job.optimizer;
+  j.max_iterations = c->dbg_job.max_iterations;
+  j.fixed_iterations = c->dbg_job.fixed_iterations;
+  j.job_full = c->dbg_job.job_full;
+  j.ticket = c->dbg_job.ticket;
+  const bool same = std::memcmp(&j, &c->dbg_job, sizeof(AlignJob)) == 0;
+  std::memcpy(&j, &c->dbg_job, sizeof(AlignJob));
+  if (!same) {
+    c->dbg_search = false;
+    return fail(GICP_ESTATE, "the ctx changed since gicp_debug_search_begin (parameters, covariances, shard, cells or tie tree): begin again");
+  }
+  return GICP_OK;
+}
+
+gicp_status gicp_debug_search_step(gicp_ctx* c, const double* pose16, int rec, double* H36, double* b6, double* cost,
+                                   int32_t* ncorr) {
+  if (!c || !pose16) return fail(GICP_EINVAL, "null argument");
+  if (!c->dbg_search || !c->src.cloud || !c->tgt.cloud || c->src.cloud->n != c->last_nsrc)
+    return fail(GICP_ESTATE, "gicp_debug_search_begin first");
+  gicp_status s = set_device(c);
+  if (s) return s;
+  s = debug_search_job_current(c);
+  if (s) return s;
+  begin_ties(c);
+  const int ns = c->src.cloud->n;
+  const int nblocks = linearize_blocks(ns);
+  AlignJob* jd = c->job_dev.as<AlignJob>();
+  char* const sd = c->state_dev.as<char>();
+  // the words k_lm_step would have left for this iteration: the pose, not done, the recording flag
+  struct {
+    double Rt[12];
+    int done, rec;
+  } w;
+  for (int r = 0; r < 3; ++r) {
+    for (int cc = 0; cc < 3; ++cc) w.Rt[3 * r + cc] = pose16[4 * r + cc];
+    w.Rt[9 + r] = pose16[4 * r + 3];
+  }
+  w.done = 0;
+  w.rec = rec ? 1 : 0;
+  static_assert(offsetof(AlignState, t) == offsetof(AlignState, R) + 72, "R, t: 12 consecutive doubles");
+  // Until the target has its tie tree a step may meet a tie it cannot resolve
+  // (tie_pending): the state it found is kept, so that the tree is built and
+  // the same step runs again on what the previous step left.
+  const bool may_rerun = c->job_host->tie_detect && !c->job_host->tgt_nf.nodes;
+  const SearchLayout sl(ns);
+  const size_t nb_state = (sizeof(AlignState) + 255) / 256 * 256, nb_corr = (sizeof(int) * (size_t)ns + 255) / 256 * 256,
+               nb_search = sl.tasks;   // every per-query array and the counters (the task list is consumed per iteration)
+  if (may_rerun) HIP_TRY(c->dbg_snap.ensure(nb_state + 2 * nb_corr + nb_search));
+  char* const snap = c->dbg_snap.as<char>();
+  auto carry = [&](bool save) -> gicp_status {
+    const struct {
+      void* p;
+      size_t off, n;
+    } part[4] = {{c->state_dev.p, 0, sizeof(AlignState)},
+                 {c->corr.p, nb_state, sizeof(int) * (size_t)ns},
+                 {c->sqd.p, nb_state + nb_corr, sizeof(float) * (size_t)ns},
+                 {c->search.p, nb_state + 2 * nb_corr, nb_search}};
+    for (const auto& q : part)
+      HIP_TRY(hipMemcpyAsync(save ? (void*)(snap + q.off) : q.p, save ? q.p : (void*)(snap + q.off), q.n,
+                             hipMemcpyDeviceToDevice, c->stream));
+    return GICP_OK;
+  };
+  for (int rerun = 0;; ++rerun) {
+    if (may_rerun) {
+      s = carry(rerun == 0);
+      if (s) return s;
+    }
+    HIP_TRY(hipMemcpyAsync(sd + offsetof(AlignState, R), w.Rt, sizeof(w.Rt), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(sd + offsetof(AlignState, done), &w.done, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(sd + offsetof(AlignState, rec), &w.rec, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    s = enqueue_iteration(c, jd, nblocks, nullptr);
+    if (s) return s;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->state_host, c->state_dev.p, sizeof(AlignState), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->state_slot = 0;
+    if (!final_state(c).tie_pending || rerun > 0 || !may_rerun) break;
+    s = ensure_tie_tree(c);
+    if (s) return s;
+    // the device job learns of the tree (k_align_init would also reset the state)
+    const NfTreeData* tt = c->tgt.cloud->nf.get();
+    c->job_host->tgt_nf = tt->dev();
+    c->job_host->tgt_nf_status = tt->status.as<int>();
+    HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(jd) + offsetof(AlignJob, tgt_nf_status), &c->job_host->tgt_nf_status,
+                           sizeof(c->job_host->tgt_nf_status), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(jd) + offsetof(AlignJob, tgt_nf), &c->job_host->tgt_nf,
+                           sizeof(NfTreeDev), hipMemcpyHostToDevice, c->stream));
+    std::memcpy(&c->dbg_job, c->job_host, sizeof(AlignJob));
+  }
+  const AlignState& st = final_state(c);
+  s = check_ties(c);
+  if (s) return s;
+  if (st.tie_err || st.tie_pending)
+    return fail(GICP_EHIP, "nanoflann tie order: a tied correspondence could not be re-run (bits " +
+                               std::to_string(st.tie_err) + ")");
+  if (H36) std::memcpy(H36, st.final_hessian, sizeof(double) * 36);
+  if (cost) *cost = st.final_cost;
+  if (ncorr) *ncorr = st.num_corr;
+  if (b6) std::memcpy(b6, st.last_b, sizeof(double) * 6);
+  c->have_align = true;
+  return GICP_OK;
+}
+
+// The per-query search state of the last iteration, in the caller's order
+// (tests).  Copies only: the permutation is applied on the host.
+gicp_status gicp_debug_search_state(gicp_ctx* c, int32_t* corr, float* sqd, uint32_t* sec, float* ref4, float* refp4,
+                                    float* wr, int32_t* any_rec_out, size_t n) {
+  if (!c) return fail(GICP_EINVAL, "null ctx");
+  if (!c->have_align || !c->src.cloud || !c->tgt.cloud) return fail(GICP_ESTATE, "no linearization");
+  if ((int)n != c->src.cloud->n || c->last_nsrc != (int)n) return fail(GICP_EINVAL, "n != source size");
+  gicp_status s = set_device(c);
+  if (s) return s;
+  const SearchLayout sl(c->src.cloud->n);
+  if (c->search.bytes < sl.total) return fail(GICP_ESTATE, "no search state");
+  const int nt = c->tgt.cloud->n;
+  std::vector<int> sperm(n), tperm((size_t)nt), hcorr(n);
+  std::vector<float> hsqd(n);
+  std::vector<unsigned> hsec(n);
+  std::vector<float4> href(n), hrefp(n), hq(n);
+  const char* u = c->search.as<char>();
+  HIP_TRY(hipStreamSynchronize(c->stream));   // (an align's queued no-op chunk)
+  int any_rec = 0;
+  HIP_TRY(hipMemcpy(&any_rec, c->state_dev.as<char>() + offsetof(AlignState, any_rec), sizeof(int), hipMemcpyDeviceToHost));
+  if (any_rec_out) *any_rec_out = any_rec;
+  HIP_TRY(hipMemcpy(sperm.data(), c->src.cloud->perm.p, sizeof(int) * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(tperm.data(), c->tgt.cloud->perm.p, sizeof(int) * (size_t)nt, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hcorr.data(), c->corr.p, sizeof(int) * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hsqd.data(), c->sqd.p, sizeof(float) * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hsec.data(), u + sl.sec, sizeof(unsigned) * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(href.data(), u + sl.ref, sizeof(float4) * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hrefp.data(), u + sl.ref_p, sizeof(float4) * n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hq.data(), u + sl.qstate, sizeof(float4) * n, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < n; ++i) {
+    const size_t o = (size_t)sperm[i];
+    if (o >= n) return fail(GICP_EHIP, "source permutation out of range");
+    if (corr) corr[o] = (hcorr[i] >= 0 && hcorr[i] < nt) ? tperm[(size_t)hcorr[i]] : -1;
+    if (sqd) sqd[o] = hsqd[i];
+    if (sec) sec[o] = hsec[i];
+    if (ref4) std::memcpy(ref4 + 4 * o, &href[i], sizeof(float4));   // raw: the search reads it only with any_rec set
+    if (refp4) {
+      int j;
+      std::memcpy(&j, &hrefp[i].w, sizeof(int));
+      const int jo = (j >= 0 && j < nt) ? tperm[(size_t)j] : -1;   // int bits, as on the device
+      refp4[4 * o] = hrefp[i].x;
+      refp4[4 * o + 1] = hrefp[i].y;
+      refp4[4 * o + 2] = hrefp[i].z;
+      std::memcpy(refp4 + 4 * o + 3, &jo, sizeof(int));
+    }
+    if (wr) wr[o] = hq[i].w;
+  }
   return GICP_OK;
 }
 

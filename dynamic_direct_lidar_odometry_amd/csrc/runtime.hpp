@@ -394,6 +394,10 @@ struct gicp_ctx {
   unsigned long long ticket = 0;   // aligns launched (AlignJob::ticket)
   int* flag_host = nullptr;       // pinned
   bool have_align = false;        // a linearize ran against the current src/tgt
+  bool dbg_search = false;        // gicp_debug_search_begin's job and state are on the device (gicp_debug_search_step)
+  DevBuf dbg_snap;                // a step's carried state, kept until the target has its tie tree
+  AlignJob dbg_job{};             // the job gicp_debug_search_begin sent (+ the tie tree a step added): a step runs only while
+                                  // the ctx would still build the same one
   int last_nsrc = 0;
   // chunk graphs of the last kGraphSets launch geometries (least recently
   // used evicted)
@@ -1037,6 +1041,7 @@ inline void invalidate_align(gicp_ctx* c) {
   c->have_align = false;
   c->job_last_valid = false;
   c->fresh_ok = false;
+  c->dbg_search = false;
 }
 
 }  // namespace rt

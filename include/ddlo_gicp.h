@@ -336,6 +336,35 @@ typedef struct gicp_lm_state {
  * of a sharded align).  Layout: DESIGN.md "Normal-equation moments". */
 gicp_status gicp_debug_lm_step(struct gicp_ctx* ctx, const gicp_lm_state* in, const double* slab, int nrows,
                                const double* mom80, gicp_lm_state* out);
+/* The correspondence search pose by pose; test entries.  An align's search
+ * carries state from one outer iteration to the next (the previous matches,
+ * the pose they were found at, recorded reuse references); these drive it
+ * through a scripted sequence of poses and recording decisions.
+ * gicp_debug_search_begin: what gicp_linearize does before its iteration (the
+ * job, with Gauss-Newton and an iteration bound that is never reached, and
+ * the init kernel).  gicp_debug_search_step: one outer iteration of an align
+ * (the same kernels and launch geometry) at pose16 (row-major 4x4 double),
+ * with the recording flag the previous LM step would have chosen (rec 0/1),
+ * on the state the previous step left; returns that linearization's H, b,
+ * cost and matched count.  The pose the iteration's own step writes is
+ * replaced by the next call's.  A tie met before the target has its tie tree
+ * builds it and runs the same step again on the same carried state.
+ * gicp_debug_search_state: copies of the last iteration's per-query search
+ * state (after a step or a gicp_align), per source point in the caller's
+ * order; nothing on the device changes.  corr: original target indices or
+ * -1; sqd: +inf where nothing was found; sec: the raw word (all ones: not
+ * searched); ref4: the raw (q_ref, B^2), B^2 < 0 without a reference; refp4:
+ * (p1, original target index as int bits, -1: none within the bound); wr:
+ * the walk radius (< 0: not searched); any_rec: the state's flag that an
+ * iteration has recorded -- the search reads ref4 / refp4 only when it is
+ * set, whatever an earlier align left in them.  Any output may be NULL.
+ * A step refuses (GICP_ESTATE) once the ctx would no longer build the job
+ * that gicp_debug_search_begin sent (a setter was called since). */
+gicp_status gicp_debug_search_begin(struct gicp_ctx* ctx);
+gicp_status gicp_debug_search_step(struct gicp_ctx* ctx, const double* pose16, int rec, double* H36, double* b6,
+                                   double* cost, int32_t* num_correspondences);
+gicp_status gicp_debug_search_state(struct gicp_ctx* ctx, int32_t* corr, float* sqd, uint32_t* sec, float* ref4,
+                                    float* refp4, float* wr, int32_t* any_rec, size_t n);
 /* Device time accounting of the linearize kernel inside align (HIP events
  * captured in the align graph).  Off by default. */
 gicp_status gicp_set_profiling(struct gicp_ctx* ctx, int enable);
