@@ -133,10 +133,28 @@ size_t crop_box_tmp_bytes(int n);
 int compact_flagged(hipStream_t s, const float4* in, int n, float4* out, const int* keep, int* pos, void* tmp,
                     size_t tmp_bytes, int* count_host, int* pin);
 // crop > 0: the crop box (points inside [-crop, crop]^3 removed) folded into the same pass
+// order: ddlo_voxel_order.  0 (input order) launches what it always did and reads neither
+// oscratch nor anything of voxel_order.hip; 1 (PCL order) sums every voxel's points in the order
+// std::sort leaves them and needs oscratch = voxel_order_scratch_ints(n) ints of its own.
 int voxel_grid(hipStream_t s, const float4* in, int n, float leaf, float4* out, int* scratch, void* tmp, size_t tmp_bytes,
-               int* count_host, float crop, int* pin, CropCentre centre = CropCentre());
+               int* count_host, float crop, int* pin, CropCentre centre = CropCentre(), int order = 0,
+               int* oscratch = nullptr);
 size_t voxel_tmp_bytes(int n);
 constexpr size_t voxel_scratch_ints(int n) { return 7 * (size_t)n + 16 + 6 * 64; }
+
+// voxel_order.hip: std::sort's permutation of (key, index) pairs on the device.
+// A segment of at most this many pairs finishes its recursion in LDS.
+constexpr int kVoxelOrderHandOver = 512;
+size_t sort_order_scratch_ints(int n);
+size_t voxel_order_scratch_ints(int n);
+// the introsort loop (partition levels, depth-limit heap sorts) in place on (keys, idx)[0, ns): ns = n,
+// or the count of a compaction (pos = exclusive sum of keep over n), read on the device.  The caller's
+// stable sort by key completes std::sort.  No host synchronisation.
+void launch_sort_order(hipStream_t s, unsigned* keys, int* idx, int n, const int* pos, const int* keep, int* scratch);
+// the voxel pass's pairs with key != UINT_MAX compacted in input order and permuted; the tails of
+// *ck_out / *ci_out (in oscratch) keep UINT_MAX / 0.  -2: tmp too small (an exclusive sum over n).
+int voxel_order_pairs(hipStream_t s, const unsigned* keys, const int* idx, int n, int* oscratch, void* tmp,
+                      size_t tmp_bytes, unsigned** ck_out, int** ci_out);
 void median_range_async(hipStream_t s, const float4* in, int n, float* d, float* result, void* tmp, size_t tmp_bytes,
                         float* out);
 size_t median_tmp_bytes(int n);

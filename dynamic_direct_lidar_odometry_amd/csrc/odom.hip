@@ -467,6 +467,10 @@ struct ddlo_odom {
   hipStream_t s = nullptr;
   // scratch (device)
   DevBuf up, a, b, keep, pos, vscratch, cubtmp, medtmp, rng, rng_sorted, cat_pts, cat_cov;
+  // ddlo_odom_set_voxel_order: the summation order of the scan and keyframe voxel
+  // filters, and the scratch only the PCL order needs
+  int voxel_order = DDLO_VOXEL_ORDER_INPUT;
+  DevBuf voscratch;
   // pinned host memory: [0] the median range of the current scan, [4..19] the
   // voxel / crop count read-back (int)
   PinBuf median_pin;
@@ -551,13 +555,16 @@ gicp_status preprocess(ddlo_odom* o, int n, bool crop, double crop_size, bool vo
   HIP_TRY(o->vscratch.ensure(sizeof(int) * voxel_scratch_ints(std::max(n, 1))));
   gicp_status st = ensure_tmp(o, std::max(n, 1));
   if (st) return st;
+  const int order = o->voxel_order;
+  if (vox && order != DDLO_VOXEL_ORDER_INPUT)
+    HIP_TRY(o->voscratch.ensure(sizeof(int) * voxel_order_scratch_ints(std::max(n, 1))));
   int m = n;
   if (crop && vox && m > 0) {
     // one pass: the voxel filter over the points the crop box keeps (their
     // bbox, their input order), one count read-back instead of two
     int c = 0;
     if (voxel_grid(o->s, o->a.as<float4>(), m, (float)leaf, o->b.as<float4>(), o->vscratch.as<int>(), o->cubtmp.p,
-                   o->cubtmp.bytes, &c, (float)crop_size, o->count_pin))
+                   o->cubtmp.bytes, &c, (float)crop_size, o->count_pin, CropCentre(), order, o->voscratch.as<int>()))
       return fail(GICP_EHIP, "voxel filter scratch too small");
     if (c >= 0) {
       *nout = c;
@@ -582,7 +589,7 @@ gicp_status preprocess(ddlo_odom* o, int n, bool crop, double crop_size, bool vo
   if (vox && m > 0) {
     int c = 0;
     if (voxel_grid(o->s, o->a.as<float4>(), m, (float)leaf, o->b.as<float4>(), o->vscratch.as<int>(), o->cubtmp.p,
-                   o->cubtmp.bytes, &c, 0.f, o->count_pin))
+                   o->cubtmp.bytes, &c, 0.f, o->count_pin, CropCentre(), order, o->voscratch.as<int>()))
       return fail(GICP_EHIP, "voxel filter scratch too small");
     if (c >= 0) {  // -1: grid overflow, the reference keeps the cloud unchanged
       finite = true;
@@ -1315,15 +1322,35 @@ gicp_status ddlo_odom_ctx(ddlo_odom* o, int which, gicp_ctx** ctx) {
   return GICP_OK;
 }
 
+gicp_status ddlo_odom_set_voxel_order(ddlo_odom* o, int order) {
+  if (!o) return fail(GICP_EINVAL, "null handle");
+  if (order != DDLO_VOXEL_ORDER_INPUT && order != DDLO_VOXEL_ORDER_PCL) return fail(GICP_EINVAL, "unknown voxel order");
+  o->voxel_order = order;
+  return GICP_OK;
+}
+
+gicp_status ddlo_odom_get_voxel_order(const ddlo_odom* o, int* order) {
+  if (!o || !order) return fail(GICP_EINVAL, "null argument");
+  *order = o->voxel_order;
+  return GICP_OK;
+}
+
 gicp_status ddlo_preprocess(int device, const float* xyz, size_t n, size_t stride, double crop_size, double leaf,
                             float* out, size_t cap, size_t* nout) {
+  return ddlo_preprocess_ordered(device, xyz, n, stride, crop_size, leaf, DDLO_VOXEL_ORDER_INPUT, out, cap, nout);
+}
+
+gicp_status ddlo_preprocess_ordered(int device, const float* xyz, size_t n, size_t stride, double crop_size, double leaf,
+                                    int order, float* out, size_t cap, size_t* nout) {
   if ((!xyz && n) || !nout || stride < 12 || stride % 4 || n > (size_t)INT32_MAX / 2) return fail(GICP_EINVAL, "invalid argument");
+  if (order != DDLO_VOXEL_ORDER_INPUT && order != DDLO_VOXEL_ORDER_PCL) return fail(GICP_EINVAL, "unknown voxel order");
   ddlo_odom_params p;
   ddlo_odom_default_params(&p);
   ddlo_odom* o = nullptr;
   gicp_status st = ddlo_odom_create(device, &p, &o);
   if (st) return st;
   std::unique_ptr<ddlo_odom, gicp_status (*)(ddlo_odom*)> guard(o, ddlo_odom_destroy);
+  o->voxel_order = order;
   *nout = 0;
   if (n == 0) return GICP_OK;
   HIP_TRY(o->up.ensure((n - 1) * stride + 12));

@@ -173,9 +173,11 @@ __global__ void k_voxel_tail(const unsigned* __restrict__ uniq, int n, int* __re
   }
 }
 
-// Centroid of each run of equal voxel index: float sums in input order
-// (the radix sort is stable), divided by the count (CentroidPoint /
-// AccumulatorXYZ).
+// Centroid of each run of equal voxel index: float sums in the order of
+// `order` within the run, divided by the count (CentroidPoint /
+// AccumulatorXYZ).  The radix sort is stable, so that is the order its input
+// had: input order (DDLO_VOXEL_ORDER_INPUT), or the order std::sort's
+// partitions and heap sorts left (DDLO_VOXEL_ORDER_PCL, voxel_order.hip).
 __global__ __launch_bounds__(256) void k_voxel_centroids(const float4* __restrict__ in, const int* __restrict__ order,
                                                          const int* __restrict__ offsets, const int* __restrict__ counts,
                                                          int nruns, float4* __restrict__ out) {
@@ -297,8 +299,11 @@ size_t voxel_tmp_bytes(int n) {
 // grid overflows: the caller copies the input, as the reference does).
 // pin: 16 ints of pinned host memory (the read-back of small).  small needs
 // no clearing: every slot the host reads ([5], [6], [8], [9]) is written.
+// order 1 (PCL): the pairs of the points in the pass are compacted and permuted
+// as std::sort's introsort loop leaves them (oscratch) before the stable sort;
+// the same launches follow, and no read-back is added.
 int voxel_grid(hipStream_t s, const float4* in, int n, float leaf, float4* out, int* scratch, void* tmp, size_t tmp_bytes,
-               int* count_host, float crop, int* pin, CropCentre centre) {
+               int* count_host, float crop, int* pin, CropCentre centre, int order_mode, int* oscratch) {
   *count_host = 0;
   if (n <= 0) return 0;
   unsigned* keys = reinterpret_cast<unsigned*>(scratch);
@@ -316,8 +321,17 @@ int voxel_grid(hipStream_t s, const float4* in, int n, float leaf, float4* out, 
   k_voxel_keys<<<cdiv_l(n, 256), 256, 0, s>>>(in, n, inv, inv, inv, crop, centre, part, small, keys, idx);
   size_t need = voxel_tmp_bytes(n);
   if (need > tmp_bytes) return -2;
+  const unsigned* sort_keys = keys;
+  const int* sort_idx = idx;
+  if (order_mode != 0) {
+    unsigned* ck = nullptr;
+    int* ci = nullptr;
+    if (!oscratch || voxel_order_pairs(s, keys, idx, n, oscratch, tmp, tmp_bytes, &ck, &ci)) return -2;
+    sort_keys = ck;
+    sort_idx = ci;
+  }
   size_t t = tmp_bytes;
-  (void)hipcub::DeviceRadixSort::SortPairs(tmp, t, keys, keys_sorted, idx, order, n, 0, 32, s);
+  (void)hipcub::DeviceRadixSort::SortPairs(tmp, t, sort_keys, keys_sorted, sort_idx, order, n, 0, 32, s);
   t = tmp_bytes;
   (void)hipcub::DeviceRunLengthEncode::Encode(tmp, t, keys_sorted, uniq, counts, small + 8, n, s);
   k_voxel_tail<<<1, 64, 0, s>>>(uniq, n, small);

@@ -50,6 +50,9 @@ struct ddlo_seg {
   // objects and the static cloud: the segments' pixel lists and the object
   // records on the device; the packed scan, the removed pixels and the filter scratch
   ddlo::rt::DevBuf zimg, dcsr, dobj, ddrop, f4, f4b, keep, pos, vscratch, cubtmp;
+  // ddlo_seg_set_voxel_order: the static cloud's voxel pass, and the scratch only the PCL order needs
+  int voxel_order = 0;
+  ddlo::rt::DevBuf voscratch;
   bool have_objects = false;          // objects holds the last scan's records
   std::vector<ddlo_seg_object> objects;   // every segment's record of the last scan (before the ratio test)
   // seg_csr: the last scan's segments are on the device (host labelling: dcsr

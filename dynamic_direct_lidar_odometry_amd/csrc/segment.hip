@@ -927,6 +927,7 @@ gicp_status seg_static_begin(ddlo_seg* o, const float centre[3], const float4** 
   HIP_TRY(o->pos.ensure(sizeof(int) * (size_t)n));
   HIP_TRY(o->vscratch.ensure(sizeof(int) * voxel_scratch_ints(n)));
   HIP_TRY(o->cubtmp.ensure(std::max(crop_box_tmp_bytes(n), voxel_tmp_bytes(n))));
+  if (o->voxel_order != 0) HIP_TRY(o->voscratch.ensure(sizeof(int) * voxel_order_scratch_ints(n)));
   launch_pack4(o->s, o->raw.as<unsigned char>(), o->raw_stride, n, o->f4.as<float4>());
   return GICP_OK;
 }
@@ -939,7 +940,8 @@ gicp_status seg_static_finish(ddlo_seg* o, const float centre[3], double crop_si
   int m = -1;
   if (leaf > 0) {   // the crop box folded into the voxel pass (as the driver's preprocessing does)
     if (voxel_grid(o->s, o->f4.as<float4>(), n, (float)leaf, o->f4b.as<float4>(), o->vscratch.as<int>(), o->cubtmp.p,
-                   o->cubtmp.bytes, &m, crop ? (float)crop_size : 0.f, o->cnt_pin.as<int>(), cc))
+                   o->cubtmp.bytes, &m, crop ? (float)crop_size : 0.f, o->cnt_pin.as<int>(), cc, o->voxel_order,
+                   o->voscratch.as<int>()))
       return fail(GICP_EHIP, "voxel filter scratch too small");
   }
   if (m < 0) {   // no voxel filter, or its grid overflows (the reference then keeps the cloud as it is)
@@ -1079,6 +1081,19 @@ gicp_status ddlo_seg_set_labelling(ddlo_seg* o, int mode) {
     o->csr_ready = o->csr_len_ready = false;
   }
   o->labelling = mode;
+  return GICP_OK;
+}
+
+gicp_status ddlo_seg_set_voxel_order(ddlo_seg* o, int order) {
+  if (!o) return fail(GICP_EINVAL, "null handle");
+  if (order != DDLO_VOXEL_ORDER_INPUT && order != DDLO_VOXEL_ORDER_PCL) return fail(GICP_EINVAL, "unknown voxel order");
+  o->voxel_order = order;
+  return GICP_OK;
+}
+
+gicp_status ddlo_seg_get_voxel_order(const ddlo_seg* o, int* order) {
+  if (!o || !order) return fail(GICP_EINVAL, "null argument");
+  *order = o->voxel_order;
   return GICP_OK;
 }
 

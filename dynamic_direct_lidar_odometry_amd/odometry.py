@@ -75,6 +75,16 @@ class DynamicParams(C.Structure):
 NONSTATIC_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(SegObject), C.c_size_t, C.POINTER(C.c_uint8))
 
 
+# ddlo_voxel_order: the order a voxel filter sums a voxel's points in
+VOXEL_ORDER_INPUT, VOXEL_ORDER_PCL = 0, 1
+
+
+class SortOrderStats(C.Structure):
+    """ddlo_sort_order_stats."""
+    _fields_ = [("levels", C.c_int32), ("global_levels", C.c_int32), ("lds_segments", C.c_int32),
+                ("heap_segments", C.c_int32), ("heap_longest", C.c_int32), ("threshold", C.c_int32)]
+
+
 _SIGS_DONE = False
 
 
@@ -105,6 +115,10 @@ def _lib():
             "ddlo_odom_submap": (I, [P, P, S, C.POINTER(S)]),
             "ddlo_odom_ctx": (I, [P, I, C.POINTER(P)]),
             "ddlo_preprocess": (I, [I, P, S, S, D, D, P, S, C.POINTER(S)]),
+            "ddlo_preprocess_ordered": (I, [I, P, S, S, D, D, I, P, S, C.POINTER(S)]),
+            "ddlo_odom_set_voxel_order": (I, [P, I]),
+            "ddlo_odom_get_voxel_order": (I, [P, C.POINTER(I)]),
+            "ddlo_debug_sort_order": (I, [I, P, S, P, C.POINTER(SortOrderStats)]),
             "ddlo_median_range": (I, [I, P, S, S, C.POINTER(C.c_float)]),
             "ddlo_convex_hull": (I, [P, I, P, I, C.POINTER(I)]),
             "ddlo_concave_hull": (I, [P, I, D, P, I, C.POINTER(I)]),
@@ -162,6 +176,18 @@ class Odometry:
             self.close()
         except Exception:
             pass
+
+    def set_voxel_order(self, order: int):
+        """ddlo_odom_set_voxel_order: VOXEL_ORDER_INPUT (default) or VOXEL_ORDER_PCL for the scan and the
+        keyframe voxel filters, from the next scan on.  The dynamic and tracked entries build keyframes
+        through the Segmentation handle too: set it there as well."""
+        _check(self.L.ddlo_odom_set_voxel_order(self.h, int(order)))
+
+    @property
+    def voxel_order(self) -> int:
+        m = C.c_int()
+        _check(self.L.ddlo_odom_get_voxel_order(self.h, C.byref(m)))
+        return m.value
 
     def process(self, points) -> OdomResult:
         a = _xyz(points)
@@ -295,14 +321,30 @@ class Odometry:
         return out[:n.value]
 
 
-def preprocess(points, crop_size: float = 0.0, leaf: float = 0.0, device: int = 0) -> np.ndarray:
-    """Device crop box (points inside [-s, s]^3 removed) then voxel filter."""
+def preprocess(points, crop_size: float = 0.0, leaf: float = 0.0, device: int = 0,
+               order: int = VOXEL_ORDER_INPUT) -> np.ndarray:
+    """Device crop box (points inside [-s, s]^3 removed) then voxel filter.  order: the voxel filter sums
+    each voxel's points in input order (VOXEL_ORDER_INPUT) or in pcl::VoxelGrid's (VOXEL_ORDER_PCL)."""
     a = _xyz(points)
     out = np.zeros((max(a.shape[0], 1), 3), np.float32)
     n = C.c_size_t()
-    _check(_lib().ddlo_preprocess(device, _ptr(a), a.shape[0], 12, float(crop_size), float(leaf), _ptr(out),
-                                  out.shape[0], C.byref(n)))
+    if order == VOXEL_ORDER_INPUT:
+        _check(_lib().ddlo_preprocess(device, _ptr(a), a.shape[0], 12, float(crop_size), float(leaf), _ptr(out),
+                                      out.shape[0], C.byref(n)))
+    else:
+        _check(_lib().ddlo_preprocess_ordered(device, _ptr(a), a.shape[0], 12, float(crop_size), float(leaf),
+                                              int(order), _ptr(out), out.shape[0], C.byref(n)))
     return out[:n.value]
+
+
+def sort_order(keys, device: int = 0):
+    """ddlo_debug_sort_order: (perm, stats) of std::sort on the pairs (keys[i], i) compared by key alone,
+    computed on the device: perm[r] is the original index at rank r; stats is a SortOrderStats."""
+    k = np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1)
+    perm = np.zeros(max(k.shape[0], 1), np.int32)
+    st = SortOrderStats()
+    _check(_lib().ddlo_debug_sort_order(device, _ptr(k) if k.shape[0] else None, k.shape[0], _ptr(perm), C.byref(st)))
+    return perm[:k.shape[0]], st
 
 
 def median_range(points, stride: int = 12, device: int = 0) -> float:

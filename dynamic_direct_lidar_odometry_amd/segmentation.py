@@ -144,6 +144,8 @@ def _lib():
             "ddlo_seg_label_device": (I, [I, C.POINTER(SegParams), P, P, P, F, P, P, S, C.POINTER(C.c_int32)]),
             "ddlo_seg_set_labelling": (I, [P, I]),
             "ddlo_seg_get_labelling": (I, [P, C.POINTER(I)]),
+            "ddlo_seg_set_voxel_order": (I, [P, I]),
+            "ddlo_seg_get_voxel_order": (I, [P, C.POINTER(I)]),
             "ddlo_seg_labelling_stats": (I, [P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
             "ddlo_seg_objects": (I, [P, F, P, S, C.POINTER(S)]),
             "ddlo_seg_objects_from": (I, [I, P, S, I, I, P, P, S, F, P, S, C.POINTER(S)]),
@@ -281,6 +283,17 @@ class Segmentation:
         if mode not in LABELLING:
             raise ValueError('labelling must be "host" or "device"')
         _check(self.L.ddlo_seg_set_labelling(self.h, LABELLING[mode]))
+
+    def set_voxel_order(self, order: int):
+        """ddlo_seg_set_voxel_order: 0 (input order, the default) or 1 (pcl::VoxelGrid's order) for the voxel
+        pass of static_cloud / static_cloud_tracks, from the next call on."""
+        _check(self.L.ddlo_seg_set_voxel_order(self.h, int(order)))
+
+    @property
+    def voxel_order(self) -> int:
+        m = C.c_int()
+        _check(self.L.ddlo_seg_get_voxel_order(self.h, C.byref(m)))
+        return m.value
 
     def labelling_stats(self):
         """Device mode: (components whose push prefix was replayed, longest prefix) of the last scan."""

@@ -64,6 +64,9 @@ gicp_status ddlo_map_destroy(struct ddlo_map* m);
  * voxel_filter_use: pcl::VoxelGrid at leaf_size over the keyframe's finite
  * points, the centroids appended in voxel-index order; if the voxel index
  * would overflow an int the keyframe is appended unfiltered, as PCL does.
+ * The map's filter (here and in ddlo_map_points / ddlo_map_save_pcd) sums a
+ * voxel's points in input order: the PCL order that ddlo_odom_set_voxel_order
+ * selects for the driver's filters has no counterpart here.
  * Filter off: the finite points are appended in input order.  Non-finite
  * points are dropped in both modes (see above).  *added (optional) = points
  * appended.  A map that would exceed INT_MAX points: GICP_EINVAL. */

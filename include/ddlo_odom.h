@@ -200,6 +200,34 @@ gicp_status ddlo_odom_ctx(struct ddlo_odom* o, int which, struct gicp_ctx** ctx)
  * of out in points). */
 gicp_status ddlo_preprocess(int device, const float* xyz, size_t n, size_t stride_bytes, double crop_size, double leaf,
                             float* out, size_t cap, size_t* nout);
+/* ddlo_preprocess with the voxel filter's summation order chosen
+ * (ddlo_voxel_order, ddlo_segment.h).  DDLO_VOXEL_ORDER_INPUT gives
+ * ddlo_preprocess's bits; DDLO_VOXEL_ORDER_PCL gives pcl::VoxelGrid's.  A
+ * grid overflow and a cloud without a finite point behave the same in both. */
+gicp_status ddlo_preprocess_ordered(int device, const float* xyz, size_t n, size_t stride_bytes, double crop_size,
+                                    double leaf, int order, float* out, size_t cap, size_t* nout);
+/* The summation order of the driver's own voxel filters: the scan filter and
+ * the keyframe (submap) filter of every ddlo_odom_process* entry, from the
+ * next scan on.  An unknown value is GICP_EINVAL and changes nothing.  The
+ * keyframes of the dynamic and tracked entries also pass through the caller's
+ * segmentation handle: see ddlo_seg_set_voxel_order.  The global map's own
+ * filter keeps input order. */
+gicp_status ddlo_odom_set_voxel_order(struct ddlo_odom* o, int order);
+gicp_status ddlo_odom_get_voxel_order(const struct ddlo_odom* o, int* order);
+/* The sort behind DDLO_VOXEL_ORDER_PCL on its own (tests): perm_out[r] = the
+ * original index at rank r after std::sort of the pairs (keys[i], i) compared
+ * by key alone, computed on the device.  stats (optional): which paths the
+ * input took. */
+typedef struct ddlo_sort_order_stats {
+  int32_t levels;          /* partition levels run (the depth limit is 2 floor(log2 n)) */
+  int32_t global_levels;   /* of those, levels run on segments too long for one workgroup's LDS */
+  int32_t lds_segments;    /* segments handed to the LDS finish */
+  int32_t heap_segments;   /* segments heap-sorted at the depth limit */
+  int32_t heap_longest;    /* the longest of them */
+  int32_t threshold;       /* a segment of at most this many pairs is handed over */
+} ddlo_sort_order_stats;
+gicp_status ddlo_debug_sort_order(int device, const uint32_t* keys, size_t n, int32_t* perm_out,
+                                  ddlo_sort_order_stats* stats_out);
 /* The median range behind the spaciousness metric on its own (computeSpaciousness,
  * odom.cc:981-1001): element n / 2 of the sorted ranges float(sqrt(x^2 + y^2 +
  * z^2)) of the n points as they are, with no preprocessing; n == 0 gives 0.

@@ -167,5 +167,7 @@ gicp_status ddlo_seg_label(const ddlo_seg_params* p, const float* range, const f
 /* ddlo_seg_projection, ddlo_seg_default_projection, ddlo_seg_process_cloud, ddlo_seg_projection_maps,
    ddlo_seg_point_classes */
 #include "ddlo_seg_project.h"
+/* ddlo_voxel_order, ddlo_seg_set_voxel_order, ddlo_seg_get_voxel_order */
+#include "ddlo_voxel_order.h"
 
 #endif /* DDLO_SEGMENT_H */
