@@ -78,6 +78,11 @@ __device__ __forceinline__ void inv3(const double m[9], double r[9]) {
   r[8] = (m[0] * m[4] - m[1] * m[3]) * id;
 }
 
+// values.array().max(1e-3) of the reference (nano_gicp_impl.hpp:427, 431) is
+// the comparison a < b ? b : a, which hands a NaN through; fmax would turn it
+// into 1e-3.
+__device__ __forceinline__ double clamp_below(double a) { return a < 1e-3 ? 1e-3 : a; }
+
 // regularisation of a covariance (nano_gicp_impl.hpp:401-437)
 __device__ inline void regularize(const double C[9], int method, double out[6]) {
   double R[9];
@@ -108,9 +113,9 @@ __device__ inline void regularize(const double C[9], int method, double out[6]) 
     if (method == 3) {  // PLANE
       vals[0] = 1; vals[1] = 1; vals[2] = 1e-3;
     } else if (method == 1) {  // MIN_EIG
-      for (int i = 0; i < 3; ++i) vals[i] = fmax(sv[i], 1e-3);
-    } else {  // NORMALIZED_MIN_EIG
-      for (int i = 0; i < 3; ++i) vals[i] = fmax(sv[i] / sv[0], 1e-3);
+      for (int i = 0; i < 3; ++i) vals[i] = clamp_below(sv[i]);
+    } else {  // NORMALIZED_MIN_EIG: 0 / 0 on a zero covariance stays NaN, in all six entries
+      for (int i = 0; i < 3; ++i) vals[i] = clamp_below(sv[i] / sv[0]);
     }
     for (int i = 0; i < 9; ++i) R[i] = 0.0;
     for (int j = 0; j < 3; ++j) {

@@ -29,6 +29,11 @@
  * PCL, which are absent, so it is NOT pinned against the reference binary:
  * it is cross-checked against an independent numpy/scipy implementation
  * (tests/test_oracle_numpy.py) — "parity unpinned" for that half.
+ * calculate_covariances and regularize are held, on rank 0 to 3
+ * neighbourhoods, to an extended-precision restatement that shares no
+ * operation sequence with sym_eig3 (tests/cov_ref.py,
+ * tests/test_cov_cases_cpu.py): what any correct SVD must give, the NaN of
+ * NORMALIZED_MIN_EIG on a zero covariance included.
  *
  * fp32 query transform order: q_i = (R_i0*x + R_i1*y) + (R_i2*z + t_i), no
  * FMA — Eigen 3.3's coefficient-based lazy product of the 3x4 affine block
