@@ -119,6 +119,12 @@ void launch_cov_remap(hipStream_t s, const double* old_cov6, const int* old_inv_
 // preprocess.hip (odometry driver): see the kernels there for the reference
 // filters they restate.  Scratch sizes: *_tmp_bytes (hipcub temporaries).
 void launch_pack4(hipStream_t s, const unsigned char* raw, size_t stride, int n, float4* out);
+// the row/column filter's registration pass (ddlo_downsample.h): |S| of a rows x cols image, the
+// number of S's pixels below n, and the pack of exactly those, ascending, into out (returns that number)
+long long rowcol_size(int rows, int cols, int row_step, int col_step);
+int rowcol_count(int n, int rows, int cols, int row_step, int col_step);
+int launch_pack4_rowcol(hipStream_t s, const unsigned char* raw, size_t stride, int n, int rows, int cols, int row_step,
+                        int col_step, float4* out);
 // centre of the crop box (CropBox::setTranslation); the origin by default
 struct CropCentre {
   float x = 0.f, y = 0.f, z = 0.f;

@@ -471,6 +471,8 @@ struct ddlo_odom {
   // filters, and the scratch only the PCL order needs
   int voxel_order = DDLO_VOXEL_ORDER_INPUT;
   DevBuf voscratch;
+  // ddlo_odom_set_downsampling: the row/column filter's registration pass in front of preprocess()
+  int ds_use = 0, ds_row = 1, ds_col = 1, ds_rows = 1, ds_cols = 1;
   // pinned host memory: [0] the median range of the current scan, [4..19] the
   // voxel / crop count read-back (int)
   PinBuf median_pin;
@@ -868,6 +870,42 @@ gicp_status submap_keyframes(ddlo_odom* o, bool* changed) {
 
 void copy_pose(const float* T, float* out) { std::memcpy(out, T, sizeof(float) * 16); }
 
+// the n uploaded points of o->up into o->a as float4; returns how many.  With
+// the row/column filter on: only the pixels of S below n, ascending, unless
+// |S| > n, when ExtractIndices reports an error and passes the scan on as it is
+int pack_scan(ddlo_odom* o, int n, size_t stride) {
+  if (o->ds_use && rowcol_size(o->ds_rows, o->ds_cols, o->ds_row, o->ds_col) <= (long long)n)
+    return launch_pack4_rowcol(o->s, o->up.as<unsigned char>(), stride, n, o->ds_rows, o->ds_cols, o->ds_row, o->ds_col,
+                               o->a.as<float4>());
+  launch_pack4(o->s, o->up.as<unsigned char>(), stride, n, o->a.as<float4>());
+  return n;
+}
+
+// what ddlo_odom_set_downsampling asks of a scan and of the segmentation
+// handle, checked before anything of the scan or the driver's state is touched
+gicp_status downsampling_check(const ddlo_odom* o, size_t n, const DynStep* dyn) {
+  int use = 0, row = 1, col = 1;
+  if (dyn) {
+    gicp_status st = ddlo_seg_get_downsampling(dyn->seg, &use, &row, &col);
+    if (st) return st;
+    if ((use != 0) != (o->ds_use != 0))
+      return fail(GICP_EINVAL, "downsampling is on for one of the driver and the segmentation only");
+  }
+  if (!o->ds_use) return GICP_OK;
+  if (dyn && dyn->cloud) return fail(GICP_EINVAL, "downsampling needs an organized scan: not with the _cloud entries");
+  if (n != (size_t)o->ds_rows * (size_t)o->ds_cols) return fail(GICP_EINVAL, "downsampling: scan size != rows x cols");
+  if (dyn) {
+    ddlo_seg_params sp;
+    gicp_status st = seg_get_params(dyn->seg, &sp);
+    if (st) return st;
+    if (sp.rows != o->ds_rows || sp.cols != o->ds_cols)
+      return fail(GICP_EINVAL, "downsampling: the segmentation's rows x cols differ from the driver's");
+    if (row != o->ds_row || col != o->ds_col)
+      return fail(GICP_EINVAL, "downsampling: the segmentation's steps differ from the driver's");
+  }
+  return GICP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -972,7 +1010,9 @@ static gicp_status process_scan(ddlo_odom* o, const float* xyz, size_t n, size_t
                                 const DynStep* dyn) {
   if (!o || !res || (!xyz && n) || stride < 12 || stride % 4) return fail(GICP_EINVAL, "invalid argument");
   if (n > (size_t)INT32_MAX / 2) return fail(GICP_EINVAL, "scan too large");
-  gicp_status st = set_device(o->s2s);
+  gicp_status st = downsampling_check(o, n, dyn);
+  if (st) return st;
+  st = set_device(o->s2s);
   if (st) return st;
   begin_ties(o->s2s);
   begin_ties(o->s2m);
@@ -1016,11 +1056,13 @@ static gicp_status process_scan(ddlo_odom* o, const float* xyz, size_t n, size_t
   HIP_TRY(hipMemcpyAsync(o->up.p, xyz, (n - 1) * stride + 12, hipMemcpyHostToDevice, o->s));
   if (o->timing) o->t_phase[9] += std::chrono::duration<double>(clk::now() - t0).count();
   HIP_TRY(o->a.ensure(sizeof(float4) * n));
-  launch_pack4(o->s, o->up.as<unsigned char>(), stride, N, o->a.as<float4>());
+  // the registration scan: every point, or only the row/column filter's pixels
+  // (odom.cc:445-455); o->up keeps the whole scan for the segmentation
+  const int NR = pack_scan(o, N, stride);
   mark(0);
-  int m = N;
+  int m = NR;
   bool scan_finite = false;
-  st = preprocess(o, N, o->p.crop_use != 0, o->p.crop_size, o->p.vf_scan_use != 0, o->p.vf_scan_res, &m, &scan_finite);
+  st = preprocess(o, NR, o->p.crop_use != 0, o->p.crop_size, o->p.vf_scan_use != 0, o->p.vf_scan_res, &m, &scan_finite);
   if (st) return st;
   res->scan_points = m;
   mark(1);
@@ -1340,8 +1382,32 @@ gicp_status ddlo_preprocess(int device, const float* xyz, size_t n, size_t strid
   return ddlo_preprocess_ordered(device, xyz, n, stride, crop_size, leaf, DDLO_VOXEL_ORDER_INPUT, out, cap, nout);
 }
 
-gicp_status ddlo_preprocess_ordered(int device, const float* xyz, size_t n, size_t stride, double crop_size, double leaf,
-                                    int order, float* out, size_t cap, size_t* nout) {
+gicp_status ddlo_odom_set_downsampling(ddlo_odom* o, int use, int row_step, int col_step, int rows, int cols) {
+  if (!o) return fail(GICP_EINVAL, "null handle");
+  if (row_step < 1 || col_step < 1 || rows < 1 || cols < 1 || (long long)rows * cols > INT32_MAX / 2)
+    return fail(GICP_EINVAL, "downsampling: steps, rows and cols must be >= 1");
+  o->ds_use = use != 0;
+  o->ds_row = row_step;
+  o->ds_col = col_step;
+  o->ds_rows = rows;
+  o->ds_cols = cols;
+  return GICP_OK;
+}
+
+gicp_status ddlo_odom_get_downsampling(const ddlo_odom* o, int* use, int* row_step, int* col_step, int* rows, int* cols) {
+  if (!o) return fail(GICP_EINVAL, "null handle");
+  if (use) *use = o->ds_use;
+  if (row_step) *row_step = o->ds_row;
+  if (col_step) *col_step = o->ds_col;
+  if (rows) *rows = o->ds_rows;
+  if (cols) *cols = o->ds_cols;
+  return GICP_OK;
+}
+
+// ddlo_preprocess_ordered / ddlo_preprocess_downsampled (rows > 0: through the row/column filter)
+static gicp_status preprocess_entry(int device, const float* xyz, size_t n, size_t stride, int rows, int cols, int row_step,
+                                    int col_step, double crop_size, double leaf, int order, float* out, size_t cap,
+                                    size_t* nout) {
   if ((!xyz && n) || !nout || stride < 12 || stride % 4 || n > (size_t)INT32_MAX / 2) return fail(GICP_EINVAL, "invalid argument");
   if (order != DDLO_VOXEL_ORDER_INPUT && order != DDLO_VOXEL_ORDER_PCL) return fail(GICP_EINVAL, "unknown voxel order");
   ddlo_odom_params p;
@@ -1351,14 +1417,18 @@ gicp_status ddlo_preprocess_ordered(int device, const float* xyz, size_t n, size
   if (st) return st;
   std::unique_ptr<ddlo_odom, gicp_status (*)(ddlo_odom*)> guard(o, ddlo_odom_destroy);
   o->voxel_order = order;
+  if (rows > 0) {
+    st = ddlo_odom_set_downsampling(o, 1, row_step, col_step, rows, cols);
+    if (st) return st;
+  }
   *nout = 0;
   if (n == 0) return GICP_OK;
   HIP_TRY(o->up.ensure((n - 1) * stride + 12));
   HIP_TRY(hipMemcpyAsync(o->up.p, xyz, (n - 1) * stride + 12, hipMemcpyHostToDevice, o->s));
   HIP_TRY(o->a.ensure(sizeof(float4) * n));
-  launch_pack4(o->s, o->up.as<unsigned char>(), stride, (int)n, o->a.as<float4>());
+  const int nr = pack_scan(o, (int)n, stride);
   int m = 0;
-  st = preprocess(o, (int)n, crop_size > 0, crop_size, leaf > 0, leaf, &m);
+  st = preprocess(o, nr, crop_size > 0, crop_size, leaf > 0, leaf, &m);
   if (st) return st;
   *nout = (size_t)m;
   if (out && m > 0) {
@@ -1366,6 +1436,19 @@ gicp_status ddlo_preprocess_ordered(int device, const float* xyz, size_t n, size
     return read_xyz(o->s, o->a.as<float4>(), (size_t)m, out);
   }
   return GICP_OK;
+}
+
+gicp_status ddlo_preprocess_ordered(int device, const float* xyz, size_t n, size_t stride, double crop_size, double leaf,
+                                    int order, float* out, size_t cap, size_t* nout) {
+  return preprocess_entry(device, xyz, n, stride, 0, 0, 1, 1, crop_size, leaf, order, out, cap, nout);
+}
+
+gicp_status ddlo_preprocess_downsampled(int device, const float* xyz, size_t n, size_t stride, int rows, int cols,
+                                        int row_step, int col_step, double crop_size, double leaf, int order, float* out,
+                                        size_t cap, size_t* nout) {
+  if (rows < 1 || cols < 1 || row_step < 1 || col_step < 1)
+    return fail(GICP_EINVAL, "downsampling: steps, rows and cols must be >= 1");
+  return preprocess_entry(device, xyz, n, stride, rows, cols, row_step, col_step, crop_size, leaf, order, out, cap, nout);
 }
 
 gicp_status ddlo_median_range(int device, const float* xyz, size_t n, size_t stride, float* median) {

@@ -1,6 +1,9 @@
 // preprocess.hip — device-side scan preprocessing and keyframe plumbing of
 // the odometry driver (odom.hip), SURVEY.md §8(f) ranks 1 and 3:
 //
+//   k_pack4_rowcol             the row/column filter's registration pass
+//                              (pcl::ExtractIndices, odom.cc:445-455), as a
+//                              masked pack of the upload
 //   k_crop_keep / compaction   pcl::CropBox with setNegative(true)
 //                              (odom.cc:114-119,460-465)
 //   voxel_grid()               pcl::VoxelGrid<PointXYZI>::applyFilter
@@ -38,6 +41,25 @@ __global__ __launch_bounds__(256) void k_pack4(const unsigned char* __restrict__
   if (i >= n) return;
   const float* p = reinterpret_cast<const float*>(raw + (size_t)i * stride);
   out[i] = make_float4(p[0], p[1], p[2], 0.f);
+}
+
+// ---- upload through the row/column filter (odom.cc:445-455) ----
+// pcl::ExtractIndices, keep-organized, with the index set S = { r W + c : r a
+// multiple of row_step, c a multiple of col_step } makes every pixel outside
+// S NaN, and the crop box and the voxel filter then skip those.  This packs
+// only the pixels of S below n, in ascending index order: output k is pixel
+// (k / nc) row_step W + (k % nc) col_step, nc = ceil(W / col_step).  Ascending
+// k is ascending pixel index, so the pixels below n are a prefix of the
+// outputs; the host counts them (rowcol_count) and sizes the grid by it.
+__global__ __launch_bounds__(256) void k_pack4_rowcol(const unsigned char* __restrict__ raw, size_t stride, int n, int W,
+                                                      int row_step, int col_step, int nc, int m,
+                                                      float4* __restrict__ out) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= m) return;
+  const long long pix = (long long)(k / nc) * row_step * W + (long long)(k % nc) * col_step;
+  if (pix >= n) return;   // (never: m counts the pixels below n)
+  const float* p = reinterpret_cast<const float*>(raw + (size_t)pix * stride);
+  out[k] = make_float4(p[0], p[1], p[2], 0.f);
 }
 
 // ---- crop box (negative: keep the points strictly outside [-s, s]^3) ----
@@ -482,6 +504,27 @@ size_t median_tmp_bytes(int n) {
 
 void launch_pack4(hipStream_t s, const unsigned char* raw, size_t stride, int n, float4* out) {
   k_pack4<<<cdiv_l(n, 256), 256, 0, s>>>(raw, stride, n, out);
+}
+long long rowcol_size(int rows, int cols, int row_step, int col_step) {
+  return (long long)((rows + row_step - 1) / row_step) * ((cols + col_step - 1) / col_step);
+}
+int rowcol_count(int n, int rows, int cols, int row_step, int col_step) {
+  const int nr = (rows + row_step - 1) / row_step, nc = (cols + col_step - 1) / col_step;
+  long long cnt = 0;
+  for (int i = 0; i < nr; ++i) {
+    const long long base = (long long)i * row_step * cols;
+    if (base >= n) break;
+    cnt += std::min<long long>(nc, (n - base + col_step - 1) / col_step);
+  }
+  return (int)cnt;   // <= n
+}
+int launch_pack4_rowcol(hipStream_t s, const unsigned char* raw, size_t stride, int n, int rows, int cols, int row_step,
+                        int col_step, float4* out) {
+  const int m = rowcol_count(n, rows, cols, row_step, col_step);
+  if (m > 0)
+    k_pack4_rowcol<<<cdiv_l(m, 256), 256, 0, s>>>(raw, stride, n, cols, row_step, col_step,
+                                                  (cols + col_step - 1) / col_step, m, out);
+  return m;
 }
 void launch_transform4(hipStream_t s, const float4* pts, const int* perm, int n, const float* T12, float4* out) {
   T34 T;

@@ -524,7 +524,7 @@ __global__ __launch_bounds__(kLblThreads) void k_lbl_drop(const int* __restrict_
                                                           const int* __restrict__ pix, float4* __restrict__ pts) {
   const int l = ids[blockIdx.y];
   for (int i = off[l] + blockIdx.x * blockDim.x + threadIdx.x; i < off[l + 1]; i += gridDim.x * blockDim.x)
-    pts[pix[i]] = make_float4(NAN, NAN, NAN, 0.f);
+    pts[pix[i]] = make_float4(NAN, NAN, NAN, kRemovedW);   // (a pixel named twice: the same bits)
 }
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }

@@ -77,7 +77,13 @@ bool label_device_window_ok(const ddlo_seg_params& p);
 // holds the labels, w.rec the record, w.seg_off / w.seg_pix the segments.
 gicp_status label_device_run(hipStream_t s, const ddlo_seg_params& p, LabelDev& w, const LabelDevIn& in);
 
-// pts[pixel] = NaN for the pixels of the segments ids[0 .. nids) (device ints, each in 1 .. segments)
+// The removed flag of the static cloud's packed scan: the drop kernels (here, segment.hip,
+// seg_tracks.hip) write (NaN, NaN, NaN, kRemovedW) over a removed pixel, the pack writes w = 0, so a
+// removed pixel and a no-return pixel stay apart for the row/column filter's keyframe pass.  Nothing
+// else reads w.
+constexpr float kRemovedW = 1.f;
+
+// pts[pixel] = NaN (w = kRemovedW) for the pixels of the segments ids[0 .. nids) (device ints, each in 1 .. segments)
 gicp_status label_device_drop(hipStream_t s, const LabelDev& w, const int* ids, int nids, float4* pts);
 
 gicp_status seg_check_params(const ddlo_seg_params* p);

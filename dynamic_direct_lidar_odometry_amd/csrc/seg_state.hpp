@@ -53,7 +53,13 @@ struct ddlo_seg {
   // ddlo_seg_set_voxel_order: the static cloud's voxel pass, and the scratch only the PCL order needs
   int voxel_order = 0;
   ddlo::rt::DevBuf voscratch;
-  bool have_objects = false;          // objects holds the last scan's records
+  // ddlo_seg_set_downsampling: the row/column filter's keyframe pass between the removal and the
+  // crop (seg_static_finish): the workgroups' removed counts and the pass's control words, and
+  // whether the last pass met |S| > n' (read back with the filters' count, cnt_pin[16])
+  int ds_use = 0, ds_row = 1, ds_col = 1;
+  ddlo::rt::DevBuf ds_part;
+  bool ds_skipped = false;
+  bool have_objects = false;         // objects holds the last scan's records
   std::vector<ddlo_seg_object> objects;   // every segment's record of the last scan (before the ratio test)
   // seg_csr: the last scan's segments are on the device (host labelling: dcsr
   // holds them) / their lengths are in csr_len.  Reset with every scan.
@@ -110,9 +116,11 @@ struct SegCsr {
 gicp_status seg_csr(ddlo_seg* s, SegCsr* out);
 
 // ddlo_seg_static_cloud* in three steps.  begin: the checks, the scratch, the
-// scan packed into s->f4.  Then the caller's removal: NaN over points of
-// s->f4, on s->s.  finish: the voxel filter or the crop box into *pts / *count
-// (valid until the next call on s); complete when it returns.
+// scan packed into s->f4.  Then the caller's removal: (NaN, NaN, NaN,
+// kRemovedW) over points of s->f4, on s->s.  finish: the row/column filter's
+// keyframe pass if it is on (ddlo_seg_set_downsampling), then the voxel filter
+// or the crop box into *pts / *count (valid until the next call on s);
+// complete when it returns.
 gicp_status seg_static_begin(ddlo_seg* s, const float centre[3], const float4** pts, int* count);
 gicp_status seg_static_finish(ddlo_seg* s, const float centre[3], double crop_size, double leaf, const float4** pts,
                               int* count);

@@ -69,15 +69,16 @@ __global__ __launch_bounds__(kTrkThreads) void k_trk_gather(const TrkEntry* __re
 
 // A pixel can be in several removed lists (a stale list and the current
 // one of another track overlap where an object stood still): every writer
-// stores the same bits, (NaN, NaN, NaN, 0), so the result does not depend on
-// which store lands last.  Neither atomics nor a pass that removes duplicates.
+// stores the same bits, (NaN, NaN, NaN, kRemovedW: the removed flag of the
+// row/column filter's keyframe pass), so the result does not depend on which
+// store lands last.  Neither atomics nor a pass that removes duplicates.
 __global__ __launch_bounds__(kTrkThreads) void k_trk_drop(const int2* __restrict__ ranges,
                                                           const int* __restrict__ pool, float4* __restrict__ pts,
                                                           int npix) {
   const int2 r = ranges[blockIdx.y];   // (offset, length)
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < r.y; i += gridDim.x * blockDim.x) {
     const int p = pool[r.x + i];
-    if ((unsigned)p < (unsigned)npix) pts[p] = make_float4(NAN, NAN, NAN, 0.f);
+    if ((unsigned)p < (unsigned)npix) pts[p] = make_float4(NAN, NAN, NAN, kRemovedW);
   }
 }
 

@@ -434,9 +434,124 @@ __global__ __launch_bounds__(kObjThreads) void k_seg_objects(SegObjArgs a) {
 // the pixels of the removed segments made NaN in the packed scan: the crop
 // box / voxel pass drops non-finite points, so the removal, the finite test
 // and the crop are one keep predicate there
+// w = kRemovedW marks the pixel as removed (a no-return pixel is NaN with the
+// w = 0 the pack gave it): the row/column filter's keyframe pass tells them
+// apart.  A pixel named twice gets the same bits twice.
 __global__ __launch_bounds__(256) void k_static_drop(const int* __restrict__ pix, int m, float4* __restrict__ pts) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < m) pts[pix[j]] = make_float4(NAN, NAN, NAN, 0.f);
+  if (j < m) pts[pix[j]] = make_float4(NAN, NAN, NAN, kRemovedW);
+}
+
+// ---- the row/column filter's keyframe pass (odom.cc:902-906) ----------------
+// The reference extracts the non-static pixels without keep-organized and
+// then runs the filter of the registration pass, with its absolute index set
+// S, over the compacted cloud of n' points: the point at position j stays if j
+// is in S.  Pixel p, if not removed, has position j = p - (removed pixels
+// before p); a no-return pixel keeps its position.  Two launches, a workgroup
+// of kDsThreads per kDsThreads consecutive pixels, one pixel per thread:
+//   k_ds_count  the removed pixels of every workgroup's pixels -> part[workgroup]
+//   k_ds_keep   every workgroup sums part (the workgroups before it: its
+//               offset; all of them: n' = n - total, and with it the |S| <= n'
+//               decision, taken here by every workgroup alike), ranks its own
+//               pixels and writes the verdicts: keep_out[p] (the debug entry),
+//               or NaN over the points that leave (pts; the crop box / voxel
+//               pass drops them).
+// Within a workgroup: one 64-bit ballot gives a lane the removed pixels before
+// it in its wavefront, the four wavefront totals go through LDS.  Every lane
+// reaches the ballot and the shuffles (a pixel past n counts as not removed).
+// Integer arithmetic throughout: exact for any number of workgroups.  Each
+// workgroup reads all of part: quadratic in the workgroups, a few hundred for
+// the images this runs on, where exactness matters and speed does not.
+constexpr int kDsThreads = 256, kDsWaves = kDsThreads / 64;
+
+// whether this thread's pixel was removed; *before = the removed pixels of the workgroup's before
+// it, *total = all of them.  sh: kDsWaves ints.
+__device__ bool ds_block_rank(const unsigned char* __restrict__ flags, const float4* __restrict__ pts, int n, int* sh,
+                              int* before, int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int p = blockIdx.x * kDsThreads + threadIdx.x;
+  const bool removed = p < n && (flags ? flags[p] != 0 : pts[p].w != 0.f);
+  const unsigned long long b = __ballot(removed);
+  if (lane == 0) sh[wave] = __popcll(b);
+  __syncthreads();
+  int run = __popcll(b & ((1ull << lane) - 1ull)), all = 0;
+#pragma unroll
+  for (int w = 0; w < kDsWaves; ++w) {
+    if (w < wave) run += sh[w];
+    all += sh[w];
+  }
+  *before = run;
+  *total = all;
+  return removed;
+}
+
+__global__ __launch_bounds__(kDsThreads) void k_ds_count(const unsigned char* __restrict__ flags,
+                                                         const float4* __restrict__ pts, int n, int* __restrict__ part) {
+  __shared__ int sh[kDsWaves];
+  int before, total;
+  (void)ds_block_rank(flags, pts, n, sh, &before, &total);
+  if (threadIdx.x == 0) part[blockIdx.x] = total;
+}
+
+// ctrl[0] = 1 if |S| > n' (nothing filtered), ctrl[1] = the removed pixels
+__global__ __launch_bounds__(kDsThreads) void k_ds_keep(const unsigned char* __restrict__ flags, float4* __restrict__ pts,
+                                                        int n, const int* __restrict__ part, int W, int row_step,
+                                                        int col_step, long long s_size,
+                                                        unsigned char* __restrict__ keep_out, int* __restrict__ ctrl) {
+  __shared__ int sh[kDsWaves];
+  __shared__ int sums[2][kDsWaves];
+  // the removed pixels of the workgroups before this one, and of all
+  int lo = 0, all = 0;
+  for (int b = threadIdx.x; b < (int)gridDim.x; b += kDsThreads) {
+    const int v = part[b];
+    all += v;
+    if (b < (int)blockIdx.x) lo += v;
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    lo += __shfl_down(lo, d);
+    all += __shfl_down(all, d);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    sums[0][wave] = lo;
+    sums[1][wave] = all;
+  }
+  __syncthreads();
+  lo = all = 0;
+#pragma unroll
+  for (int w = 0; w < kDsWaves; ++w) {
+    lo += sums[0][w];
+    all += sums[1][w];
+  }
+  const bool skip = s_size > (long long)(n - all);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    ctrl[0] = skip ? 1 : 0;
+    ctrl[1] = all;
+  }
+  int before, total;
+  const bool removed = ds_block_rank(flags, pts, n, sh, &before, &total);
+  const int p = blockIdx.x * kDsThreads + threadIdx.x;
+  if (p >= n) return;
+  const int j = p - (lo + before);
+  const bool stays = !removed && (skip || ((j / W) % row_step == 0 && (j % W) % col_step == 0));
+  if (keep_out) keep_out[p] = stays ? 1 : 0;
+  else if (!removed && !stays) pts[p] = make_float4(NAN, NAN, NAN, 0.f);
+}
+
+inline int ds_blocks(int n) { return (int)(((long)n + kDsThreads - 1) / kDsThreads); }
+size_t downsample_scratch_ints(int n) { return (size_t)ds_blocks(n) + 2; }
+
+// flags (n bytes) or, if null, the w of pts mark the removed pixels; scratch: downsample_scratch_ints(n)
+// ints, the control words last (returned).  keep_out null: the pixels that leave become NaN in pts.
+int* launch_downsample_keep(hipStream_t s, const unsigned char* flags, float4* pts, int n, int rows, int cols,
+                            int row_step, int col_step, unsigned char* keep_out, int* scratch) {
+  const int blocks = ds_blocks(n);
+  int* const ctrl = scratch + blocks;
+  k_ds_count<<<blocks, kDsThreads, 0, s>>>(flags, pts, n, scratch);
+  k_ds_keep<<<blocks, kDsThreads, 0, s>>>(flags, pts, n, scratch, cols, row_step, col_step,
+                                          rowcol_size(rows, cols, row_step, col_step), keep_out, ctrl);
+  return ctrl;
 }
 
 // computeAllObjects' ratio test (:800-804) and avg_residuals_ on the kernel's records
@@ -579,7 +694,7 @@ gicp_status ddlo_seg_create(int device, const ddlo_seg_params* p, ddlo_seg** out
   HIP_TRY(hipStreamCreateWithFlags(&o->s, hipStreamNonBlocking));
   const size_t n = (size_t)o->p.rows * o->p.cols;
   if (o->pin.reset(n * (sizeof(float) + sizeof(int) + sizeof(float)) + n) != hipSuccess ||
-      o->cnt_pin.reset(sizeof(int) * 16) != hipSuccess) {
+      o->cnt_pin.reset(sizeof(int) * 20) != hipSuccess) {
     (void)hipStreamDestroy(o->s);
     return fail(GICP_EHIP, "pinned allocation failed");
   }
@@ -928,6 +1043,7 @@ gicp_status seg_static_begin(ddlo_seg* o, const float centre[3], const float4** 
   HIP_TRY(o->vscratch.ensure(sizeof(int) * voxel_scratch_ints(n)));
   HIP_TRY(o->cubtmp.ensure(std::max(crop_box_tmp_bytes(n), voxel_tmp_bytes(n))));
   if (o->voxel_order != 0) HIP_TRY(o->voscratch.ensure(sizeof(int) * voxel_order_scratch_ints(n)));
+  if (o->ds_use) HIP_TRY(o->ds_part.ensure(sizeof(int) * downsample_scratch_ints(n)));
   launch_pack4(o->s, o->raw.as<unsigned char>(), o->raw_stride, n, o->f4.as<float4>());
   return GICP_OK;
 }
@@ -938,6 +1054,16 @@ gicp_status seg_static_finish(ddlo_seg* o, const float centre[3], double crop_si
   const CropCentre cc{centre[0], centre[1], centre[2]};
   const bool crop = crop_size > 0;
   int m = -1;
+  int* const skipped = o->cnt_pin.as<int>() + 16;
+  *skipped = 0;
+  if (o->ds_use) {
+    // the row/column filter's keyframe pass, between the removal and the crop: NaN over the points
+    // that leave.  Its |S| <= n' decision is taken on the device; the bit comes back in stream order
+    // with the filters' count below, which is waited for anyway.
+    const int* ctrl = launch_downsample_keep(o->s, nullptr, o->f4.as<float4>(), n, o->p.rows, o->p.cols, o->ds_row,
+                                             o->ds_col, nullptr, o->ds_part.as<int>());
+    HIP_TRY(hipMemcpyAsync(skipped, ctrl, sizeof(int), hipMemcpyDeviceToHost, o->s));
+  }
   if (leaf > 0) {   // the crop box folded into the voxel pass (as the driver's preprocessing does)
     if (voxel_grid(o->s, o->f4.as<float4>(), n, (float)leaf, o->f4b.as<float4>(), o->vscratch.as<int>(), o->cubtmp.p,
                    o->cubtmp.bytes, &m, crop ? (float)crop_size : 0.f, o->cnt_pin.as<int>(), cc, o->voxel_order,
@@ -951,6 +1077,7 @@ gicp_status seg_static_finish(ddlo_seg* o, const float centre[3], double crop_si
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(o->s));
+  o->ds_skipped = *skipped != 0;
   *pts = o->f4b.as<float4>();
   *count = m;
   return GICP_OK;
@@ -1094,6 +1221,54 @@ gicp_status ddlo_seg_set_voxel_order(ddlo_seg* o, int order) {
 gicp_status ddlo_seg_get_voxel_order(const ddlo_seg* o, int* order) {
   if (!o || !order) return fail(GICP_EINVAL, "null argument");
   *order = o->voxel_order;
+  return GICP_OK;
+}
+
+gicp_status ddlo_seg_set_downsampling(ddlo_seg* o, int use, int row_step, int col_step) {
+  if (!o) return fail(GICP_EINVAL, "null handle");
+  if (row_step < 1 || col_step < 1) return fail(GICP_EINVAL, "downsampling: steps must be >= 1");
+  o->ds_use = use != 0;
+  o->ds_row = row_step;
+  o->ds_col = col_step;
+  return GICP_OK;
+}
+
+gicp_status ddlo_seg_get_downsampling(const ddlo_seg* o, int* use, int* row_step, int* col_step) {
+  if (!o) return fail(GICP_EINVAL, "null handle");
+  if (use) *use = o->ds_use;
+  if (row_step) *row_step = o->ds_row;
+  if (col_step) *col_step = o->ds_col;
+  return GICP_OK;
+}
+
+gicp_status ddlo_seg_downsampling_skipped(const ddlo_seg* o, int* skipped) {
+  if (!o || !skipped) return fail(GICP_EINVAL, "null argument");
+  *skipped = o->ds_skipped ? 1 : 0;
+  return GICP_OK;
+}
+
+gicp_status ddlo_debug_downsample_keep(int device, const uint8_t* removed, size_t n, int rows, int cols, int row_step,
+                                       int col_step, uint8_t* keep_out, int* skipped_out) {
+  if (!removed || !keep_out || rows < 1 || cols < 1 || row_step < 1 || col_step < 1 ||
+      (long long)rows * cols > INT32_MAX / 4 || n != (size_t)rows * (size_t)cols)
+    return fail(GICP_EINVAL, "invalid argument");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+    return fail(GICP_EHIP, "no HIP device " + std::to_string(device) + " (HIP library present, device not visible)");
+  HIP_TRY(hipSetDevice(device));
+  DevBuf flags, keep, scratch;
+  HIP_TRY(flags.ensure(n));
+  HIP_TRY(keep.ensure(n));
+  HIP_TRY(scratch.ensure(sizeof(int) * downsample_scratch_ints((int)n)));
+  hipStream_t s = nullptr;   // the null stream: the copies below are synchronous with it
+  HIP_TRY(hipMemcpy(flags.p, removed, n, hipMemcpyHostToDevice));
+  const int* ctrl = launch_downsample_keep(s, flags.as<unsigned char>(), nullptr, (int)n, rows, cols, row_step, col_step,
+                                           keep.as<unsigned char>(), scratch.as<int>());
+  HIP_TRY(hipGetLastError());
+  int h[2] = {0, 0};
+  HIP_TRY(hipMemcpy(h, ctrl, sizeof(h), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(keep_out, keep.p, n, hipMemcpyDeviceToHost));
+  if (skipped_out) *skipped_out = h[0];
   return GICP_OK;
 }
 

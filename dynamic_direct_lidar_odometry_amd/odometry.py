@@ -119,6 +119,10 @@ def _lib():
             "ddlo_odom_set_voxel_order": (I, [P, I]),
             "ddlo_odom_get_voxel_order": (I, [P, C.POINTER(I)]),
             "ddlo_debug_sort_order": (I, [I, P, S, P, C.POINTER(SortOrderStats)]),
+            "ddlo_odom_set_downsampling": (I, [P, I, I, I, I, I]),
+            "ddlo_odom_get_downsampling": (I, [P] + [C.POINTER(I)] * 5),
+            "ddlo_preprocess_downsampled": (I, [I, P, S, S, I, I, I, I, D, D, I, P, S, C.POINTER(S)]),
+            "ddlo_debug_downsample_keep": (I, [I, P, S, I, I, I, I, P, C.POINTER(I)]),
             "ddlo_median_range": (I, [I, P, S, S, C.POINTER(C.c_float)]),
             "ddlo_convex_hull": (I, [P, I, P, I, C.POINTER(I)]),
             "ddlo_concave_hull": (I, [P, I, D, P, I, C.POINTER(I)]),
@@ -188,6 +192,20 @@ class Odometry:
         m = C.c_int()
         _check(self.L.ddlo_odom_get_voxel_order(self.h, C.byref(m)))
         return m.value
+
+    def set_downsampling(self, use, row_step: int, col_step: int, rows: int, cols: int):
+        """ddlo_odom_set_downsampling: the organized-scan row/column filter (preprocessing/downsampling
+        {use, row, col}, detection {rows, columns}) in front of the crop box and the voxel filter, from the
+        next scan on.  With it on, scans have rows * cols points, and the dynamic and tracked entries want
+        the same setting on the Segmentation handle (Segmentation.set_downsampling)."""
+        _check(self.L.ddlo_odom_set_downsampling(self.h, int(bool(use)), int(row_step), int(col_step), int(rows),
+                                                 int(cols)))
+
+    def downsampling(self):
+        """(use, row_step, col_step, rows, cols) as set."""
+        v = [C.c_int() for _ in range(5)]
+        _check(self.L.ddlo_odom_get_downsampling(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
     def process(self, points) -> OdomResult:
         a = _xyz(points)
@@ -335,6 +353,30 @@ def preprocess(points, crop_size: float = 0.0, leaf: float = 0.0, device: int = 
         _check(_lib().ddlo_preprocess_ordered(device, _ptr(a), a.shape[0], 12, float(crop_size), float(leaf),
                                               int(order), _ptr(out), out.shape[0], C.byref(n)))
     return out[:n.value]
+
+
+def preprocess_downsampled(points, rows: int, cols: int, row_step: int, col_step: int, crop_size: float = 0.0,
+                           leaf: float = 0.0, device: int = 0, order: int = VOXEL_ORDER_INPUT) -> np.ndarray:
+    """ddlo_preprocess_downsampled: the row/column filter's registration pass over the points taken as the
+    first pixels of a rows x cols image, then preprocess()."""
+    a = _xyz(points)
+    out = np.zeros((max(a.shape[0], 1), 3), np.float32)
+    n = C.c_size_t()
+    _check(_lib().ddlo_preprocess_downsampled(device, _ptr(a), a.shape[0], 12, int(rows), int(cols), int(row_step),
+                                              int(col_step), float(crop_size), float(leaf), int(order), _ptr(out),
+                                              out.shape[0], C.byref(n)))
+    return out[:n.value]
+
+
+def downsample_keep(removed, rows: int, cols: int, row_step: int, col_step: int, device: int = 0):
+    """ddlo_debug_downsample_keep: (keep uint8[rows * cols], skipped) of the row/column filter's keyframe pass
+    over an image whose pixels flagged in `removed` were extracted before it."""
+    f = np.ascontiguousarray(removed, dtype=np.uint8).reshape(-1)
+    keep = np.zeros(max(f.shape[0], 1), np.uint8)
+    sk = C.c_int()
+    _check(_lib().ddlo_debug_downsample_keep(device, _ptr(f) if f.shape[0] else None, f.shape[0], int(rows), int(cols),
+                                             int(row_step), int(col_step), _ptr(keep), C.byref(sk)))
+    return keep[:f.shape[0]], sk.value
 
 
 def sort_order(keys, device: int = 0):

@@ -146,6 +146,9 @@ def _lib():
             "ddlo_seg_get_labelling": (I, [P, C.POINTER(I)]),
             "ddlo_seg_set_voxel_order": (I, [P, I]),
             "ddlo_seg_get_voxel_order": (I, [P, C.POINTER(I)]),
+            "ddlo_seg_set_downsampling": (I, [P, I, I, I]),
+            "ddlo_seg_get_downsampling": (I, [P, C.POINTER(I), C.POINTER(I), C.POINTER(I)]),
+            "ddlo_seg_downsampling_skipped": (I, [P, C.POINTER(I)]),
             "ddlo_seg_labelling_stats": (I, [P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
             "ddlo_seg_objects": (I, [P, F, P, S, C.POINTER(S)]),
             "ddlo_seg_objects_from": (I, [I, P, S, I, I, P, P, S, F, P, S, C.POINTER(S)]),
@@ -294,6 +297,24 @@ class Segmentation:
         m = C.c_int()
         _check(self.L.ddlo_seg_get_voxel_order(self.h, C.byref(m)))
         return m.value
+
+    def set_downsampling(self, use, row_step: int, col_step: int):
+        """ddlo_seg_set_downsampling: the row/column filter's keyframe pass inside static_cloud /
+        static_cloud_tracks, between the removal and the crop, from the next call on."""
+        _check(self.L.ddlo_seg_set_downsampling(self.h, int(bool(use)), int(row_step), int(col_step)))
+
+    def downsampling(self):
+        """(use, row_step, col_step) as set."""
+        v = [C.c_int() for _ in range(3)]
+        _check(self.L.ddlo_seg_get_downsampling(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    @property
+    def downsampling_skipped(self) -> bool:
+        """The last static cloud's keyframe pass met |S| > n' and filtered nothing."""
+        m = C.c_int()
+        _check(self.L.ddlo_seg_downsampling_skipped(self.h, C.byref(m)))
+        return bool(m.value)
 
     def labelling_stats(self):
         """Device mode: (components whose push prefix was replayed, longest prefix) of the last scan."""

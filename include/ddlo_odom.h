@@ -18,9 +18,13 @@
  * tracker does not know to be static are cut out of the scan before it may
  * become a keyframe, so that moving things never enter the submap.
  *
+ * The organized-scan row/column filter of both shipped configurations
+ * (preprocessing/downsampling, odom.cc:445-455 and :902-906) is opt-in:
+ * ddlo_odom_set_downsampling here, ddlo_seg_set_downsampling on the
+ * segmentation handle (ddlo_downsample.h states its two passes).
+ *
  * Not restated (outside the GICP path): ROS I/O, IMU gravity
- * alignment, the organized-cloud row/col downsampling filter (odom.cc:902-906),
- * publishing and trajectory files.  The object tracker (trackDetections and
+ * alignment, publishing and trajectory files.  The object tracker (trackDetections and
  * the bounding-box Kalman filter) is ddlo_track.h: ddlo_odom_process_tracked
  * runs it; ddlo_odom_process_dynamic takes a verdict through ddlo_nonstatic_fn.
  */
@@ -214,6 +218,43 @@ gicp_status ddlo_preprocess_ordered(int device, const float* xyz, size_t n, size
  * filter keeps input order. */
 gicp_status ddlo_odom_set_voxel_order(struct ddlo_odom* o, int order);
 gicp_status ddlo_odom_get_voxel_order(const struct ddlo_odom* o, int* order);
+/* The organized-scan row/column filter (ddlo_downsample.h; cfg/ddlo.yaml
+ * preprocessing/downsampling {use, row, col} and detection {rows, columns}),
+ * from the next scan on.  row_step, col_step, rows and cols must each be >= 1,
+ * otherwise GICP_EINVAL and nothing changes; use == 0 (the default) stores them
+ * and leaves every entry as it is.  With use != 0:
+ *  - ddlo_odom_process: the scan is organized, n == rows * cols; any other n is
+ *    GICP_EINVAL before the scan is touched and the driver stays usable.  The
+ *    min_num_points test stays on the raw n (odom.cc:635).  The registration
+ *    pass runs before the crop box and the voxel filter: only the pixels of S
+ *    are packed, in ascending index order, and everything after runs on
+ *    ceil(rows / row_step) * ceil(cols / col_step) points.  That gives the
+ *    bits of ExtractIndices' NaN fill: the filters only ever see the finite
+ *    points in their original order.
+ *  - ddlo_odom_process_dynamic / _tracked: seg's rows x cols and seg's own
+ *    setting (ddlo_seg_set_downsampling: use, row_step, col_step) must equal
+ *    these, otherwise GICP_EINVAL before the scan is touched.  The registration
+ *    half is ddlo_odom_process with the same setting, bit for bit; the
+ *    segmentation, the objects, the tracker and the classes see the
+ *    full-resolution scan; the residual image comes from the decimated
+ *    registration scan, as in the reference.  A keyframe added on a TRACKED
+ *    frame is the static cloud with the keyframe pass applied; keyframe 0 is
+ *    the preprocessed registration scan.
+ *  - ddlo_odom_process_dynamic_cloud / _tracked_cloud: GICP_EINVAL.  For an
+ *    unorganized cloud the reference warns and leaves preprocessPoints before
+ *    the crop box and the voxel filter too (odom.cc:447-451): a configuration
+ *    nobody wants, so it is refused here, not restated. */
+gicp_status ddlo_odom_set_downsampling(struct ddlo_odom* o, int use, int row_step, int col_step, int rows, int cols);
+gicp_status ddlo_odom_get_downsampling(const struct ddlo_odom* o, int* use, int* row_step, int* col_step, int* rows,
+                                       int* cols);
+/* The registration pass on its own (tests, benchmarks), as
+ * ddlo_preprocess_ordered: the n points are the first n pixels of a rows x
+ * cols image; the pixels of S below n are packed in ascending order, then the
+ * crop box and the voxel filter in `order`.  If |S| > n (S built for other
+ * dimensions) the scan passes unfiltered, as ExtractIndices leaves it. */
+gicp_status ddlo_preprocess_downsampled(int device, const float* xyz, size_t n, size_t stride_bytes, int rows, int cols,
+                                        int row_step, int col_step, double crop_size, double leaf, int order, float* out,
+                                        size_t cap, size_t* nout);
 /* The sort behind DDLO_VOXEL_ORDER_PCL on its own (tests): perm_out[r] = the
  * original index at rank r after std::sort of the pairs (keys[i], i) compared
  * by key alone, computed on the device.  stats (optional): which paths the

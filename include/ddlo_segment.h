@@ -169,5 +169,8 @@ gicp_status ddlo_seg_label(const ddlo_seg_params* p, const float* range, const f
 #include "ddlo_seg_project.h"
 /* ddlo_voxel_order, ddlo_seg_set_voxel_order, ddlo_seg_get_voxel_order */
 #include "ddlo_voxel_order.h"
+/* the organized-scan row/column filter: ddlo_seg_set_downsampling, ddlo_seg_get_downsampling,
+   ddlo_seg_downsampling_skipped, ddlo_debug_downsample_keep */
+#include "ddlo_downsample.h"
 
 #endif /* DDLO_SEGMENT_H */
