@@ -445,7 +445,7 @@ gicp_status cellgrid_build(gicp_ctx* c, CloudData& cd, float cap2, std::shared_p
           sizeof(float4) * (size_t)ent_base[4] > cap_bytes)
     return fail(GICP_ENOMEM, "candidate cells: the lists exceed GICP_OPT_GRID_MAX_MB");
   HIP_TRY(g->fine.ensure(sizeof(uint2) * std::max<size_t>(fine_base[4], 1)));
-  HIP_TRY(g->ent.ensure(sizeof(float4) * std::max<size_t>(ent_base[4], 1)));
+  HIP_TRY(g->ent.ensure(sizeof(float4) * ((size_t)ent_base[4] + kCgEntPad)));   // (the pad: a round's reads past the last list)
   b.fine = g->fine.as<uint2>();
   b.ent = g->ent.as<float4>();
   HIP_TRY(upload());

@@ -104,11 +104,15 @@ constexpr unsigned long long kCgNoMatch = ~0ull;       // no target point within
 constexpr unsigned long long kCgFallback = ~0ull - 1;  // no list (the walk searches the cell's queries)
 constexpr unsigned kCgFineFallback = 0xffffffffu;   // fine entry count: no list (the walk)
 constexpr int kCgMaxLevel = 3;
+// Entries allocated behind the last list: the fused lookup loads whole rounds
+// from one address and reads up to a round less one entry past a list's end
+// (moments.hip, kLookupU); what it reads there is never used.
+constexpr int kCgEntPad = 32;
 
 struct CellGridDev {
   const unsigned long long* dir;   // [nx * ny * nz] directory entries (above)
   const uint2* fine;       // per fine cell: (first entry, count)
-  const float4* ent;       // list entries: x, y, z, sorted target position (int bits)
+  const float4* ent;       // list entries: x, y, z, sorted target position (int bits); kCgEntPad more allocated
   float ox, oy, oz, inv_s; // grid origin, 1 / coarse cell size
   int nx, ny, nz;
   int outside_nomatch;     // a query outside the grid box has no target point within the bound (else the walk)

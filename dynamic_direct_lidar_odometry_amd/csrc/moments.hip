@@ -207,15 +207,20 @@ __device__ __forceinline__ void resolve_tied_corr(const AlignJob* __restrict__ j
 // The last block then publishes the state itself (publish_state).
 // LOOKUP (candidate cells without any fallback cell): the correspondence
 // lookup of k_cell_lookup is done here, one query per lane, and the match's
-// coordinates come from its list entry -- no lookup kernel, no key / sec
-// round trip.  Same keys, ties and moments as k_cell_lookup + k_moments.
-// Fused lookup: list entries loaded per round (clamped loads, no branch).
-// 16 measured 2-4 % faster on cfg 3 than 8 (the waves are 2 per SIMD, so the
-// registers are free); 12, 32, exec-masked loads, two rounds in flight (8 or
-// 12 per round) and a flat wavefront-wide scan of all 64 lists (LDS atomic
-// min per owner) all slower: the lookup is bound by the memory system's
-// throughput of scattered lines, not by the rounds' latency
-// (tools/mom_timeline.py; -DDDLO_LOOKUP_U for A/B builds).
+// coordinates are loaded once the scan has named it (tgt.pts[position]: the
+// bits of its list entry) -- no lookup kernel, no key / sec round trip.  Same
+// keys, ties and moments as k_cell_lookup + k_moments.
+// Fused lookup: list entries loaded per round, all of a round's loads issued
+// before its first entry is consumed, and scanned by the key alone without a
+// branch: about 16 instructions an entry where the branching scan that also
+// carried the coordinates took 43, and the scan's instruction issue, not the
+// memory system, was what the phase waited for
+// (profiles/lookup_scan_summary.md).  Round size: 16 measured 2-4 % faster on
+// cfg 3 than 8 (the waves are 2 per SIMD, so the registers are free); 12, 32
+// (again with the key-only scan), exec-masked loads, two rounds in flight (8
+// or 12 per round) and a flat wavefront-wide scan of all 64 lists (LDS atomic
+// min per owner) all slower (tools/mom_timeline.py; -DDDLO_LOOKUP_U for A/B
+// builds).
 #ifndef DDLO_LOOKUP_U
 #define DDLO_LOOKUP_U 16
 #endif
@@ -229,8 +234,8 @@ constexpr int kLookupU = DDLO_LOOKUP_U;
 // query, and the members' partial results are merged by a butterfly over the
 // team and moved back to the owner.  The merge (tail_merge) is the second
 // order statistic of a union of disjoint entry sets, which is what the
-// sequential scan computes, so key, second distance and coordinates are the
-// sequential scan's bit for bit whatever the partition.  H > 32: F = 1, every
+// sequential scan computes, so key and second distance are the sequential
+// scan's bit for bit whatever the partition.  H > 32: F = 1, every
 // lane goes on alone.  No LDS, no barrier; a wavefront without a long list
 // pays one ballot and one branch.  Measured (profiles/lookup_tail_summary.md):
 // kTailE0 16 and 48 and a cap of 8 on F slower, a cap of 16 the same; a member
@@ -248,35 +253,32 @@ static_assert(kTailE0 > 0 && kTailE0 % kLookupU == 0, "the common rounds end on 
 static_assert(kTailFCap >= 1 && kTailFCap <= 64 && (kTailFCap & (kTailFCap - 1)) == 0, "team size: a power of two");
 
 // One lane's lookup result over the entries it has seen: the smallest
-// (distance, position) key with its point, and the smallest distance of any
-// other entry (the second order statistic: it feeds the tie test only).
+// (distance, position) key, and the smallest distance of any other entry
+// (the second order statistic: it feeds the tie test only).
+// The key alone names the match: its coordinates are tgt.pts[position], the
+// bits k_cg_emit_* copied into the entry, loaded once after the scan.
+// d2 is kept as the distance's bit pattern and folded with the unsigned
+// minimum: on the non-negative distances of dist2 that is fminf bit for bit,
+// a NaN (any sign) is above +inf and is dropped as fminf drops it, and so is
+// the all-ones high word of the empty key ~0 -- no test for it, and none of
+// the canonicalising v_max that a float minimum of a selected word costs.
+constexpr unsigned kLookupInf = 0x7f800000u;   // +inf: no second distance yet
 struct LookupBest {
   unsigned long long bk;
-  float d2, bx, by, bz;
+  unsigned d2;
 };
 // a <- the result over the union of a's and o's (disjoint) entry sets
-__device__ __forceinline__ void tail_merge(LookupBest& a, const LookupBest& o, bool track2) {
+__device__ __forceinline__ void tail_merge(LookupBest& a, const LookupBest& o) {
   const bool take = o.bk < a.bk;
   const unsigned long long loser = take ? a.bk : o.bk;
-  if (take) {
-    a.bk = o.bk;
-    a.bx = o.bx;
-    a.by = o.by;
-    a.bz = o.bz;
-  }
-  if (track2) {
-    a.d2 = fminf(a.d2, o.d2);
-    if (loser != ~0ull) a.d2 = fminf(a.d2, __uint_as_float((unsigned)(loser >> 32)));
-  }
+  if (take) a.bk = o.bk;
+  a.d2 = min(min(a.d2, o.d2), (unsigned)(loser >> 32));
 }
 __device__ __forceinline__ LookupBest tail_shfl(const LookupBest& s, int src) {
   LookupBest r;
   r.bk = ((unsigned long long)(unsigned)__shfl((int)(unsigned)(s.bk >> 32), src) << 32) |
          (unsigned)__shfl((int)(unsigned)s.bk, src);
-  r.d2 = __shfl(s.d2, src);
-  r.bx = __shfl(s.bx, src);
-  r.by = __shfl(s.by, src);
-  r.bz = __shfl(s.bz, src);
+  r.d2 = (unsigned)__shfl((int)s.d2, src);
   return r;
 }
 
@@ -508,36 +510,47 @@ __device__ __forceinline__ void moments_body(const AlignJob* __restrict__ job, A
           cg_cell_list(G, tx, ty, tz, off, cnt);   // (no fallback cell in LOOKUP mode)
         }
       }
-      LookupBest own{~0ull, INFINITY, 0.f, 0.f, 0.f};
-      const bool track2 = tie_detect;   // the second distance only feeds the tie test
+      // (the second distance feeds the tie test only: without tie_detect it is
+      // computed all the same, one instruction an entry, and lsec is not read)
+      LookupBest own{~0ull, kLookupInf};
       constexpr int kU = kLookupU;   // loads in flight
-      // entries [k, k + kU) of the list (lo, n), against the query q, into r
+      // Entries [k, k + kU) of the list of n (k < n), against the query q, into
+      // r: no branch, the key alone.  An entry past the list's end (what the
+      // loads return there: the next list's entries, often this list's own
+      // points again) takes the all-ones word for its distance: with a real
+      // entry in front of it in every round its key is above r.bk, so it never
+      // wins, and the word is above every distance, so it never reaches d2.
+      // The loser's distance goes to d2; the empty key's high word is that
+      // same word (the first entry adds nothing to d2).
       auto consume = [&](const float4 (&pp)[kU], unsigned k, unsigned n, float qx, float qy, float qz, LookupBest& r) {
+        const unsigned left = n - k;
 #pragma unroll
         for (int u = 0; u < kU; ++u) {
-          if (k + u < n) {
-            const float dd = dist2(qx, qy, qz, pp[u].x, pp[u].y, pp[u].z);
-            const unsigned long long kk = dkey(dd, __float_as_int(pp[u].w));
-            if (kk < r.bk) {
-              if (track2 && r.bk != ~0ull) r.d2 = fminf(r.d2, __uint_as_float((unsigned)(r.bk >> 32)));
-              r.bk = kk;
-              r.bx = pp[u].x;
-              r.by = pp[u].y;
-              r.bz = pp[u].z;
-            } else if (track2) {
-              r.d2 = fminf(r.d2, dd);
-            }
-          }
+          const float dd = dist2(qx, qy, qz, pp[u].x, pp[u].y, pp[u].z);
+          const unsigned dw = (unsigned)u < left ? __float_as_uint(dd) : 0xffffffffu;
+          const unsigned long long kk = ((unsigned long long)dw << 32) | (unsigned)__float_as_int(pp[u].w);
+          const bool take = kk < r.bk;
+          r.d2 = min(r.d2, take ? (unsigned)(r.bk >> 32) : dw);
+          r.bk = take ? kk : r.bk;
         }
       };
-      auto fetch = [&](float4 (&pp)[kU], unsigned k, unsigned lo, unsigned n) {
+      // One address per round, the loads at immediate offsets.  They run up to
+      // kU - 1 entries past the list's end: inside the buffer, which
+      // cellgrid_build pads by kCgEntPad entries.  (Clamped per-load addresses
+      // cost 70 instructions a round more and measured the same or slower.)
+      static_assert(kU <= kCgEntPad, "a round reads at most kCgEntPad entries past a list's end");
+      auto fetch = [&](float4 (&pp)[kU], unsigned k, unsigned lo) {
+        const float4* const p = G.ent + (size_t)(lo + k);
 #pragma unroll
-        for (int u = 0; u < kU; ++u) pp[u] = ldg4(G.ent, lo + min(k + u, n - 1));
+        for (int u = 0; u < kU; ++u) pp[u] = ldg4(p, u);
+        // every load of the round is issued before the first entry is consumed
+        // (without the branches the scheduler would sink the loads between them)
+        __builtin_amdgcn_sched_barrier(0);
       };
       const unsigned c0 = min(cnt, kTailE0);
       for (unsigned k = 0; k < c0; k += kU) {
         float4 pp[kU];
-        fetch(pp, k, off, cnt);
+        fetch(pp, k, off);
         consume(pp, k, cnt, lqx, lqy, lqz, own);
       }
       // the remainder phase (kTailE0): lists longer than the common rounds
@@ -563,7 +576,7 @@ __device__ __forceinline__ void moments_body(const AlignJob* __restrict__ job, A
         const unsigned ocnt0 = (unsigned)__shfl((int)cnt, osrc);   // (every lane takes part: a lane left out reads as 0)
         const unsigned ocnt = owner < 0 ? 0u : ocnt0;
         const float oqx = __shfl(lqx, osrc), oqy = __shfl(lqy, osrc), oqz = __shfl(lqz, osrc);
-        LookupBest mine{~0ull, INFINITY, 0.f, 0.f, 0.f};
+        LookupBest mine{~0ull, kLookupInf};
         const unsigned stride = (unsigned)kU << lf;
         unsigned k = kTailE0 + (unsigned)kU * (unsigned)(lane & (F - 1));
 #ifdef DDLO_MOM_PROF
@@ -574,25 +587,23 @@ __device__ __forceinline__ void moments_body(const AlignJob* __restrict__ job, A
 #endif
         for (; k < ocnt; k += stride) {
           float4 pp[kU];
-          fetch(pp, k, ooff, ocnt);
+          fetch(pp, k, ooff);
           consume(pp, k, ocnt, oqx, oqy, oqz, mine);
           MOM_PROF_ROUND;
         }
 #undef MOM_PROF_ROUND
         // the team's result in every member, then in the owner
-        for (int m = 1; m < F; m <<= 1) tail_merge(mine, tail_shfl(mine, lane ^ m), track2);
+        for (int m = 1; m < F; m <<= 1) tail_merge(mine, tail_shfl(mine, lane ^ m));
         const LookupBest got = tail_shfl(mine, heavy && F > 1 ? rank << lf : lane);   // (F = 1: its own)
-        if (heavy) tail_merge(own, got, track2);
+        if (heavy) tail_merge(own, got);
 #ifdef DDLO_MOM_PROF
         mp_t[6] = (unsigned long long)H | ((unsigned long long)wave_max((float)rounds) << 8);
 #endif
       }
       const unsigned long long bk = own.bk;
-      const float d2 = own.d2, bx = own.bx, by = own.by, bz = own.bz;
+      const unsigned d2 = own.d2;
       lkey = owned ? umin64(bk, dkey(job->cap2, -1)) : dkey(INFINITY, -1);
-      const float lkd = __uint_as_float((unsigned)(lkey >> 32));
-      lsec = (owned && (unsigned)lkey != 0xffffffffu && d2 == lkd) ? (unsigned)(lkey >> 32) : 0xffffffffu;
-      b = make_float4(bx, by, bz, 0.f);
+      lsec = (owned && (unsigned)lkey != 0xffffffffu && d2 == (unsigned)(lkey >> 32)) ? (unsigned)(lkey >> 32) : 0xffffffffu;
 
       MOM_PROF(2);
     }
@@ -605,11 +616,8 @@ __device__ __forceinline__ void moments_body(const AlignJob* __restrict__ job, A
       kd = __uint_as_float((unsigned)(k >> 32));
       j = (kj != 0xffffffffu && (double)kd < max_corr2) ? (int)kj : -1;
       if (j >= 0) {
-        if constexpr (!LOOKUP) {   // (LOOKUP: a and b are in registers already)
-          a = ldg4(src.pts, i);
-          b = ldg4(tgt.pts, j);
-        }
-
+        if constexpr (!LOOKUP) a = ldg4(src.pts, i);   // (LOOKUP: a is in registers already)
+        b = ldg4(tgt.pts, j);   // (LOOKUP: the bits of the winning entry, issued with the covariances)
         load_sym6(src_cov + 6 * (size_t)i, ca);
         load_sym6(tgt_cov + 6 * (size_t)j, cb);
       }
