@@ -17,6 +17,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/ddlo_gicp.h"
 #include "gicp_types.hpp"
 
 namespace ddlo {
@@ -92,5 +93,11 @@ void launch_cg_emit_count(hipStream_t s, const CgBuild* db, int level, const int
                           unsigned* fine_n);
 void launch_cg_emit_write(hipStream_t s, const CgBuild* db, int level, const int* finals, int nfinals,
                           const unsigned* ent_off, const unsigned* fine_off, unsigned ent_base, unsigned fine_base);
+
+// cellgrid_host.hip — gicp_set_target_grid's policy, at the start of an
+// align: build the target's candidate cells for the ctx's bound when due
+namespace rt {
+gicp_status maybe_build_grid(gicp_ctx* c);
+}
 
 }  // namespace ddlo

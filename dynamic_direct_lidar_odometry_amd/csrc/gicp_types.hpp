@@ -1,4 +1,4 @@
-// gicp_types.hpp — plain data shared by the host runtime (capi.cpp) and the
+// gicp_types.hpp — plain data shared by the host runtime (capi.hip and its sibling files) and the
 // HIP kernels.  Everything here is POD so it can be memcpy'd into device
 // memory as a job descriptor.
 #pragma once

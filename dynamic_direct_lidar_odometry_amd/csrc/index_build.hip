@@ -2,7 +2,7 @@
 //
 //   K1 index build      k_pack_bbox, k_bbox_final, k_morton, k_gather,
 //                       k_key_dir / k_key_big / k_key_fine (key directory),
-//                       k_leaf_soa_boxes, k_level_boxes   (radix sort: hipcub, capi.hip)
+//                       k_leaf_soa_boxes, k_level_boxes   (radix sort: hipcub, cloud.hip)
 // Compiled with -ffp-contract=off, like every stage file: fp32 distance /
 // transform arithmetic must not be contracted into FMAs so that
 // correspondences equal the oracle's.

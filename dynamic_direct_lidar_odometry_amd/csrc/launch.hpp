@@ -1,6 +1,7 @@
 // launch.hpp — host-callable launchers of the kernels in the stage files
 // (index_build, covariance, corr_search, moments, outputs .hip) and the other
-// translation units.  The host runtime (capi.hip) only sees these plain functions.
+// translation units.  The host runtime (cloud.hip, align.hip and the other host-only
+// files) only sees these plain functions.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -271,7 +271,7 @@ typedef struct gicp_grid_info {
                                 0: the linearize is one kernel (lookup fused into the
                                 moments)                                              */
   int64_t build_status;      /* 0, or the gicp_status of a build that failed (pool or
-                                table limits, GICP_OPT_GRID_BUDGET_MB, device memory):
+                                table limits, GICP_OPT_GRID_MAX_MB, device memory):
                                 the target then stays on the walk for this bound and
                                 the align itself succeeds                             */
   int64_t scratch_bytes;     /* the build's transient device scratch at its peak (not

@@ -26,7 +26,7 @@ grid_info counters asserted on the device) and what the CPU test proves of the i
   wide         wide_box: the target indices p and d, the cell the lookup takes, the face X0
 
 The grid geometry is restated here (``Grid``) from cellgrid_build
-(dynamic_direct_lidar_odometry_amd/csrc/capi.hip) and from the lookups' fp32 cell mapping
+(dynamic_direct_lidar_odometry_amd/csrc/cellgrid_host.hip) and from the lookups' fp32 cell mapping
 (cg_cell_list, csrc/gicp_types.hpp), so that queries can be placed on cell faces; the
 device test asserts grid_info()["coarse_cells"] == prod(Grid.dims), so a drift of the
 formula fails loudly.  The sorted target position that orders every list is restated in
@@ -76,7 +76,7 @@ class Case(NamedTuple):
 # ---------------------------------------------------------------------------
 # the build's geometry and the lookups' cell mapping, restated
 class Grid:
-    """cellgrid_build's grid of a target and bound (capi.hip): the coarse cells tile the
+    """cellgrid_build's grid of a target and bound (cellgrid_host.hip): the coarse cells tile the
     target's bounding box plus M on every side."""
 
     def __init__(self, target, bound):

@@ -1,4 +1,4 @@
-"""The candidate-cell build (cellgrid.hip, cellgrid_build in capi.hip) and its three
+"""The candidate-cell build (cellgrid.hip, cellgrid_build in cellgrid_host.hip) and its three
 lookups on synthetic targets that force each path (tests/grid_cases.py; their
 properties are proven in tests/test_grid_cases_cpu.py): the fused lookup inside
 k_moments<*, true> (moments.hip; bounds 0.5 and 1.0, no fallback cell), k_cell_lookup

@@ -16,7 +16,7 @@ must pass their reference, must be searched, or are undecided.
 
 Restated from the product, with the source lines they come from:
 
-  search_knobs(), dynamic_direct_lidar_odometry_amd/csrc/capi.hip:
+  search_knobs(), dynamic_direct_lidar_odometry_amd/csrc/align.hip:
     reuse_gap 0.05, reuse_gap0 0, tri_mv 0.2, reuse_rec_eps 0.05, reuse_rec_conv 10
   "Verified reuse", csrc/corr_search.hip (k_nn_seed), in float64 from the fp32 values,
   d2(.,.) the fp32 squared distance of np_gicp.nanoflann_sqd:
@@ -24,7 +24,7 @@ Restated from the product, with the source lines they come from:
     b   = sqrt(B2 / (1 + 1e-6))
     lb2 = (b - eps)^2 (1 - 1e-6) if b > eps else -1
     with a match p1: pass iff d2(q, p1) < lb2;  with none: pass iff lb2 > cap2,
-    cap2 = nextafter(float32(bound^2), +inf)   (search_cap2, capi.hip)
+    cap2 = nextafter(float32(bound^2), +inf)   (search_cap2, align.hip)
   the walk radius of a recording search, csrc/corr_search.hip ("walk radius"):
     nextup(float32((sqrt(seed bound) + gap)^2)), gap = reuse_gap with a previous
     iteration, reuse_gap0 without (0: not widened)
