@@ -119,13 +119,14 @@ void launch_cov_remap(hipStream_t s, const double* old_cov6, const int* old_inv_
 
 // preprocess.hip (odometry driver): see the kernels there for the reference
 // filters they restate.  Scratch sizes: *_tmp_bytes (hipcub temporaries).
-void launch_pack4(hipStream_t s, const unsigned char* raw, size_t stride, int n, float4* out);
+// ioff (ddlo_intensity.h): 0 = w is 0; else w = the float ioff (>= 12) bytes into each record
+void launch_pack4(hipStream_t s, const unsigned char* raw, size_t stride, int n, float4* out, size_t ioff = 0);
 // the row/column filter's registration pass (ddlo_downsample.h): |S| of a rows x cols image, the
 // number of S's pixels below n, and the pack of exactly those, ascending, into out (returns that number)
 long long rowcol_size(int rows, int cols, int row_step, int col_step);
 int rowcol_count(int n, int rows, int cols, int row_step, int col_step);
 int launch_pack4_rowcol(hipStream_t s, const unsigned char* raw, size_t stride, int n, int rows, int cols, int row_step,
-                        int col_step, float4* out);
+                        int col_step, float4* out, size_t ioff = 0);
 // centre of the crop box (CropBox::setTranslation); the origin by default
 struct CropCentre {
   float x = 0.f, y = 0.f, z = 0.f;
@@ -143,9 +144,11 @@ int compact_flagged(hipStream_t s, const float4* in, int n, float4* out, const i
 // order: ddlo_voxel_order.  0 (input order) launches what it always did and reads neither
 // oscratch nor anything of voxel_order.hip; 1 (PCL order) sums every voxel's points in the order
 // std::sort leaves them and needs oscratch = voxel_order_scratch_ints(n) ints of its own.
+// intensity: w is a channel, averaged as x, y, z are (same points, order and count); false
+// launches the kernel it always did, and the centroids' w is 0.
 int voxel_grid(hipStream_t s, const float4* in, int n, float leaf, float4* out, int* scratch, void* tmp, size_t tmp_bytes,
                int* count_host, float crop, int* pin, CropCentre centre = CropCentre(), int order = 0,
-               int* oscratch = nullptr);
+               int* oscratch = nullptr, bool intensity = false);
 size_t voxel_tmp_bytes(int n);
 constexpr size_t voxel_scratch_ints(int n) { return 7 * (size_t)n + 16 + 6 * 64; }
 
@@ -165,9 +168,14 @@ int voxel_order_pairs(hipStream_t s, const unsigned* keys, const int* idx, int n
 void median_range_async(hipStream_t s, const float4* in, int n, float* d, float* result, void* tmp, size_t tmp_bytes,
                         float* out);
 size_t median_tmp_bytes(int n);
-void launch_transform4(hipStream_t s, const float4* pts, const int* perm, int n, const float* T12, float4* out);
+// w_orig: the intensities of the outputs (original order), or nullptr: w = 0
+void launch_transform4(hipStream_t s, const float4* pts, const int* perm, int n, const float* T12, float4* out,
+                       const float* w_orig = nullptr);
+void launch_take_w(hipStream_t s, const float4* in, int n, float* w);
 // organized raw scan -> world frame float4, pixel order kept (non-finite pixels: NaN)
-void launch_transform_raw(hipStream_t s, const unsigned char* raw, size_t stride, int n, const float* T12, float4* out);
+// ioff: as launch_pack4's
+void launch_transform_raw(hipStream_t s, const unsigned char* raw, size_t stride, int n, const float* T12, float4* out,
+                          size_t ioff = 0);
 void launch_gather_cov6(hipStream_t s, const double* cov_sorted, const int* perm, int n, double* out);
 
 }  // namespace ddlo

@@ -160,6 +160,7 @@ struct ddlo_map {
   hipEvent_t ev = nullptr;   // the odometry driver's stream -> the map's (add_odom_keyframe)
   DevBuf pts, alt;           // float4: the map, and the compaction target of the same capacity
   int size = 0, cap = 0;     // points
+  int inten = 0;             // ddlo_map_set_intensity: the points' w is the channel (else it is never read)
   // scratch (device): the upload, its float4 form, the flags and their scan, the voxel filter's, hipcub's, the boxes
   DevBuf up, a, keep, pos, vscratch, cubtmp, boxes;
   PinBuf pin;                // pinned: 16 ints, the count read-backs
@@ -207,7 +208,7 @@ gicp_status add_points(ddlo_map* m, const float4* in, int n, size_t* added) {
   if (vox) {
     HIP_TRY(m->vscratch.ensure(sizeof(int) * voxel_scratch_ints(n)));
     if (voxel_grid(m->s, in, n, (float)m->p.leaf_size, tail, m->vscratch.as<int>(), m->cubtmp.p, m->cubtmp.bytes, &c, 0.f,
-                   m->pin.as<int>()))
+                   m->pin.as<int>(), CropCentre(), 0, nullptr, m->inten != 0))
       return fail(GICP_EHIP, "voxel filter scratch too small");
     if (c < 0) vox = false;   // voxel-index overflow: PCL leaves the cloud as it is
   }
@@ -263,8 +264,9 @@ bool pack_box(const ddlo_map_box& b, double margin, float4* aabb, float4* rec) {
 
 // the map's points on the host; leaf > 0: savePcd's voxelised copy
 // (map.cc:169-177), its scratch allocated for the call: *count of them, as
-// triples in xyz (room for cap points) unless it is nullptr
-gicp_status export_points(ddlo_map* m, double leaf, float* xyz, size_t cap, size_t* count) {
+// triples in xyz (room for cap points) unless it is nullptr; xyzi: as x, y, z,
+// intensity, 16 B per point
+gicp_status export_points(ddlo_map* m, double leaf, float* xyz, size_t cap, size_t* count, bool xyzi = false) {
   *count = 0;
   if (m->size == 0) return GICP_OK;
   HIP_TRY(hipSetDevice(m->device));
@@ -277,7 +279,7 @@ gicp_status export_points(ddlo_map* m, double leaf, float* xyz, size_t cap, size
     HIP_TRY(scratch.ensure(sizeof(int) * voxel_scratch_ints(n)));
     HIP_TRY(tmp.ensure(voxel_tmp_bytes(n)));
     if (voxel_grid(m->s, src, n, (float)leaf, out.as<float4>(), scratch.as<int>(), tmp.p, tmp.bytes, &c, 0.f,
-                   m->pin.as<int>()))
+                   m->pin.as<int>(), CropCentre(), 0, nullptr, xyzi))
       return fail(GICP_EHIP, "voxel filter scratch too small");
     HIP_TRY(hipGetLastError());
     if (c < 0) c = n;   // voxel-index overflow: the map as it is
@@ -285,6 +287,11 @@ gicp_status export_points(ddlo_map* m, double leaf, float* xyz, size_t cap, size
   }
   *count = (size_t)c;
   // either way the stream is waited for: the scratch goes back to the pool idle
+  if (xyz && (size_t)c <= cap && xyzi) {
+    if (c > 0) HIP_TRY(hipMemcpyAsync(xyz, src, sizeof(float4) * (size_t)c, hipMemcpyDeviceToHost, m->s));
+    HIP_TRY(hipStreamSynchronize(m->s));
+    return GICP_OK;
+  }
   if (xyz && (size_t)c <= cap) return read_xyz(m->s, src, (size_t)c, xyz);
   HIP_TRY(hipStreamSynchronize(m->s));
   return xyz ? fail(GICP_EINVAL, "output capacity too small") : GICP_OK;
@@ -340,19 +347,53 @@ gicp_status ddlo_map_destroy(ddlo_map* m) {
   return GICP_OK;
 }
 
-gicp_status ddlo_map_add_keyframe(ddlo_map* m, const float* xyz, size_t n, size_t stride, size_t* added) {
-  if (!m || (!xyz && n) || stride < 12 || stride % 4) return fail(GICP_EINVAL, "invalid argument");
+// ddlo_map_add_keyframe (ioff = 0) and ddlo_map_add_keyframe_xyzi
+static gicp_status add_keyframe(ddlo_map* m, const float* xyz, size_t n, size_t stride, size_t ioff, size_t* added) {
   if (added) *added = 0;
   if (n == 0) return GICP_OK;
   if (n > (size_t)INT_MAX || (size_t)m->size + n > (size_t)INT_MAX)
     return fail(GICP_EINVAL, "the map would exceed INT_MAX points");
   HIP_TRY(hipSetDevice(m->device));
-  const size_t raw = (n - 1) * stride + 12;
+  const size_t raw = (n - 1) * stride + std::max<size_t>(12, ioff ? ioff + 4 : 0);
   HIP_TRY(m->up.ensure(raw));
   HIP_TRY(hipMemcpyAsync(m->up.p, xyz, raw, hipMemcpyHostToDevice, m->s));
   HIP_TRY(m->a.ensure(sizeof(float4) * n));
-  launch_pack4(m->s, m->up.as<unsigned char>(), stride, (int)n, m->a.as<float4>());
+  launch_pack4(m->s, m->up.as<unsigned char>(), stride, (int)n, m->a.as<float4>(), ioff);
   return add_points(m, m->a.as<float4>(), (int)n, added);
+}
+
+gicp_status ddlo_map_add_keyframe(ddlo_map* m, const float* xyz, size_t n, size_t stride, size_t* added) {
+  if (!m || (!xyz && n) || stride < 12 || stride % 4) return fail(GICP_EINVAL, "invalid argument");
+  return add_keyframe(m, xyz, n, stride, 0, added);
+}
+
+gicp_status ddlo_map_add_keyframe_xyzi(ddlo_map* m, const float* pts, size_t n, size_t stride, size_t offset_bytes,
+                                       size_t* added) {
+  if (!m || (!pts && n) || stride < 12 || stride % 4) return fail(GICP_EINVAL, "invalid argument");
+  if (!m->inten) return fail(GICP_EINVAL, "the map carries no intensity (ddlo_map_set_intensity)");
+  if (offset_bytes % 4 || offset_bytes < 12 || offset_bytes + 4 > stride)
+    return fail(GICP_EINVAL, "intensity offset: a multiple of 4, >= 12 and offset + 4 <= stride");
+  return add_keyframe(m, pts, n, stride, offset_bytes, added);
+}
+
+gicp_status ddlo_map_set_intensity(ddlo_map* m, int use) {
+  if (!m) return fail(GICP_EINVAL, "null handle");
+  if ((use != 0) != (m->inten != 0) && m->size != 0)
+    return fail(GICP_EINVAL, "intensity: accepted only while the map is empty");
+  m->inten = use != 0;
+  return GICP_OK;
+}
+
+gicp_status ddlo_map_get_intensity(const ddlo_map* m, int* use) {
+  if (!m || !use) return fail(GICP_EINVAL, "null argument");
+  *use = m->inten;
+  return GICP_OK;
+}
+
+gicp_status ddlo_map_points_xyzi(ddlo_map* m, double leaf, float* xyzi, size_t cap, size_t* n) {
+  if (!m || !n || (!xyzi && cap)) return fail(GICP_EINVAL, "invalid argument");
+  if (!m->inten) return fail(GICP_EINVAL, "the map carries no intensity (ddlo_map_set_intensity)");
+  return export_points(m, leaf, xyzi, cap, n, true);
 }
 
 gicp_status ddlo_map_add_odom_keyframe(ddlo_map* m, const ddlo_odom* odom, int k, size_t* added) {
@@ -364,6 +405,8 @@ gicp_status ddlo_map_add_odom_keyframe(ddlo_map* m, const ddlo_odom* odom, int k
   gicp_status st = odom_keyframe_dev(odom, k, &pts, &n, &dev, &os);
   if (st) return st;
   if (dev != m->device) return fail(GICP_EINVAL, "the map and the odometry driver are on different devices");
+  if (m->inten && !odom_has_intensity(odom))
+    return fail(GICP_EINVAL, "the map carries intensity and the odometry driver does not");
   HIP_TRY(hipSetDevice(m->device));
   // after the driver's queued work, without a host wait
   HIP_TRY(hipEventRecord(m->ev, os));
@@ -425,17 +468,22 @@ gicp_status ddlo_map_points(ddlo_map* m, double leaf, float* xyz, size_t cap, si
 gicp_status ddlo_map_save_pcd(ddlo_map* m, const char* path, double leaf) {
   if (!m || !path) return fail(GICP_EINVAL, "null argument");
   size_t n = 0;
-  std::vector<float> xyz(3 * (size_t)m->size + 1);   // (the voxelised copy is no larger; + 1: never a null pointer)
-  gicp_status st = export_points(m, leaf, xyz.data(), (size_t)m->size, &n);
+  const bool xyzi = m->inten != 0;
+  const size_t nf = xyzi ? 4 : 3;
+  std::vector<float> xyz(nf * (size_t)m->size + 1);   // (the voxelised copy is no larger; + 1: never a null pointer)
+  gicp_status st = export_points(m, leaf, xyz.data(), (size_t)m->size, &n, xyzi);
   if (st) return st;
   FILE* f = std::fopen(path, "wb");
   if (!f) return fail(GICP_EINVAL, std::string("cannot open ") + path);
   // the header pcl::PCDWriter::writeBinary gives an unorganized cloud of x, y, z
+  // (with intensity: the four fields of the reference's PointXYZI map, packed)
   std::fprintf(f,
-               "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z\nSIZE 4 4 4\nTYPE F F F\n"
-               "COUNT 1 1 1\nWIDTH %zu\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %zu\nDATA binary\n",
+               xyzi ? "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z intensity\nSIZE 4 4 4 4\n"
+                      "TYPE F F F F\nCOUNT 1 1 1 1\nWIDTH %zu\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %zu\nDATA binary\n"
+                    : "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z\nSIZE 4 4 4\nTYPE F F F\n"
+                      "COUNT 1 1 1\nWIDTH %zu\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %zu\nDATA binary\n",
                n, n);
-  const size_t wrote = n ? std::fwrite(xyz.data(), sizeof(float) * 3, n, f) : 0;
+  const size_t wrote = n ? std::fwrite(xyz.data(), sizeof(float) * nf, n, f) : 0;
   const bool closed = std::fclose(f) == 0;
   if (wrote != n || !closed) return fail(GICP_EINVAL, std::string("write failed: ") + path);
   return GICP_OK;

@@ -473,6 +473,11 @@ struct ddlo_odom {
   DevBuf voscratch;
   // ddlo_odom_set_downsampling: the row/column filter's registration pass in front of preprocess()
   int ds_use = 0, ds_row = 1, ds_col = 1, ds_rows = 1, ds_cols = 1;
+  // ddlo_odom_set_intensity: the channel in the fourth lane of up -> a -> the keyframes, and the
+  // preprocessed scan's intensities (original order) kept from preprocess() until make_keyframe
+  int inten_use = 0;
+  size_t inten_off = 0;
+  DevBuf scan_w;
   // pinned host memory: [0] the median range of the current scan, [4..19] the
   // voxel / crop count read-back (int)
   PinBuf median_pin;
@@ -566,7 +571,8 @@ gicp_status preprocess(ddlo_odom* o, int n, bool crop, double crop_size, bool vo
     // bbox, their input order), one count read-back instead of two
     int c = 0;
     if (voxel_grid(o->s, o->a.as<float4>(), m, (float)leaf, o->b.as<float4>(), o->vscratch.as<int>(), o->cubtmp.p,
-                   o->cubtmp.bytes, &c, (float)crop_size, o->count_pin, CropCentre(), order, o->voscratch.as<int>()))
+                   o->cubtmp.bytes, &c, (float)crop_size, o->count_pin, CropCentre(), order, o->voscratch.as<int>(),
+                   o->inten_use != 0))
       return fail(GICP_EHIP, "voxel filter scratch too small");
     if (c >= 0) {
       *nout = c;
@@ -591,7 +597,8 @@ gicp_status preprocess(ddlo_odom* o, int n, bool crop, double crop_size, bool vo
   if (vox && m > 0) {
     int c = 0;
     if (voxel_grid(o->s, o->a.as<float4>(), m, (float)leaf, o->b.as<float4>(), o->vscratch.as<int>(), o->cubtmp.p,
-                   o->cubtmp.bytes, &c, 0.f, o->count_pin, CropCentre(), order, o->voscratch.as<int>()))
+                   o->cubtmp.bytes, &c, 0.f, o->count_pin, CropCentre(), order, o->voscratch.as<int>(),
+                   o->inten_use != 0))
       return fail(GICP_EHIP, "voxel filter scratch too small");
     if (c >= 0) {  // -1: grid overflow, the reference keeps the cloud unchanged
       finite = true;
@@ -658,7 +665,9 @@ gicp_status make_keyframe_from_a(ddlo_odom* o, int n) {
 gicp_status make_keyframe(ddlo_odom* o, const std::shared_ptr<CloudData>& scan) {
   const int n = scan->n;
   HIP_TRY(o->a.ensure(sizeof(float4) * (size_t)n));
-  launch_transform4(o->s, scan->pts.as<float4>(), scan->perm.as<int>(), n, o->T, o->a.as<float4>());
+  // (the registration contexts never see intensity: the sorted copy's w is a point index)
+  launch_transform4(o->s, scan->pts.as<float4>(), scan->perm.as<int>(), n, o->T, o->a.as<float4>(),
+                    o->inten_use ? o->scan_w.as<float>() : nullptr);
   return make_keyframe_from_a(o, n);
 }
 
@@ -755,7 +764,8 @@ gicp_status dynamic_step(ddlo_odom* o, const DynStep& d, int npts, size_t stride
   const int npix = sp.rows * sp.cols;
   if (d.cloud) {
     ddlo_seg_projection_result pr{};
-    st = seg_project_dev(d.seg, o->s, o->up.as<unsigned char>(), stride, npts, o->T, d.proj, &pr);
+    st = seg_project_dev(d.seg, o->s, o->up.as<unsigned char>(), stride, npts, o->T, d.proj, &pr,
+                         o->inten_use ? o->inten_off : 0);
     if (st) return st;
     if (d.proj_res) *d.proj_res = pr;
   } else {
@@ -764,7 +774,7 @@ gicp_status dynamic_step(ddlo_odom* o, const DynStep& d, int npts, size_t stride
     st = seg_stage_input(d.seg, &buf, &n);
     if (st) return st;
     if (n != npts) return fail(GICP_EINVAL, "scan size != the segmentation's rows x cols");
-    launch_transform_raw(o->s, o->up.as<unsigned char>(), stride, npts, o->T, buf);
+    launch_transform_raw(o->s, o->up.as<unsigned char>(), stride, npts, o->T, buf, o->inten_use ? o->inten_off : 0);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(o->s));
   }
@@ -870,14 +880,19 @@ gicp_status submap_keyframes(ddlo_odom* o, bool* changed) {
 
 void copy_pose(const float* T, float* out) { std::memcpy(out, T, sizeof(float) * 16); }
 
+// ddlo_intensity.h's rules for the place of the intensity in a record
+bool intensity_offset_ok(size_t off, size_t stride) { return off % 4 == 0 && off >= 12 && off + 4 <= stride; }
+// the bytes of n records that are read: x, y, z of the last one, and its intensity if that is on
+size_t raw_bytes(size_t n, size_t stride, size_t ioff) { return (n - 1) * stride + std::max<size_t>(12, ioff ? ioff + 4 : 0); }
+
 // the n uploaded points of o->up into o->a as float4; returns how many.  With
 // the row/column filter on: only the pixels of S below n, ascending, unless
 // |S| > n, when ExtractIndices reports an error and passes the scan on as it is
 int pack_scan(ddlo_odom* o, int n, size_t stride) {
   if (o->ds_use && rowcol_size(o->ds_rows, o->ds_cols, o->ds_row, o->ds_col) <= (long long)n)
     return launch_pack4_rowcol(o->s, o->up.as<unsigned char>(), stride, n, o->ds_rows, o->ds_cols, o->ds_row, o->ds_col,
-                               o->a.as<float4>());
-  launch_pack4(o->s, o->up.as<unsigned char>(), stride, n, o->a.as<float4>());
+                               o->a.as<float4>(), o->inten_use ? o->inten_off : 0);
+  launch_pack4(o->s, o->up.as<unsigned char>(), stride, n, o->a.as<float4>(), o->inten_use ? o->inten_off : 0);
   return n;
 }
 
@@ -1010,6 +1025,14 @@ static gicp_status process_scan(ddlo_odom* o, const float* xyz, size_t n, size_t
                                 const DynStep* dyn) {
   if (!o || !res || (!xyz && n) || stride < 12 || stride % 4) return fail(GICP_EINVAL, "invalid argument");
   if (n > (size_t)INT32_MAX / 2) return fail(GICP_EINVAL, "scan too large");
+  if (o->inten_use && !intensity_offset_ok(o->inten_off, stride))
+    return fail(GICP_EINVAL, "intensity offset: a multiple of 4, >= 12 and offset + 4 <= stride");
+  if (dyn) {   // the keyframes come from the segmentation's static cloud: both carry the channel, or neither
+    int seg_use = 0;
+    if (gicp_status e = ddlo_seg_get_intensity(dyn->seg, &seg_use, nullptr)) return e;
+    if ((seg_use != 0) != (o->inten_use != 0))
+      return fail(GICP_EINVAL, "intensity is on for one of the driver and the segmentation only");
+  }
   gicp_status st = downsampling_check(o, n, dyn);
   if (st) return st;
   st = set_device(o->s2s);
@@ -1052,8 +1075,9 @@ static gicp_status process_scan(ddlo_odom* o, const float* xyz, size_t n, size_t
   };
   // upload + preprocessPoints (odom.cc:442-478)
   const int N = (int)n;
-  HIP_TRY(o->up.ensure((n - 1) * stride + 12));
-  HIP_TRY(hipMemcpyAsync(o->up.p, xyz, (n - 1) * stride + 12, hipMemcpyHostToDevice, o->s));
+  const size_t raw = raw_bytes(n, stride, o->inten_use ? o->inten_off : 0);
+  HIP_TRY(o->up.ensure(raw));
+  HIP_TRY(hipMemcpyAsync(o->up.p, xyz, raw, hipMemcpyHostToDevice, o->s));
   if (o->timing) o->t_phase[9] += std::chrono::duration<double>(clk::now() - t0).count();
   HIP_TRY(o->a.ensure(sizeof(float4) * n));
   // the registration scan: every point, or only the row/column filter's pixels
@@ -1065,6 +1089,10 @@ static gicp_status process_scan(ddlo_odom* o, const float* xyz, size_t n, size_t
   st = preprocess(o, NR, o->p.crop_use != 0, o->p.crop_size, o->p.vf_scan_use != 0, o->p.vf_scan_res, &m, &scan_finite);
   if (st) return st;
   res->scan_points = m;
+  if (o->inten_use) {   // o->a is the keyframe's staging buffer later: the channel is set aside now
+    HIP_TRY(o->scan_w.ensure(sizeof(float) * (size_t)std::max(m, 1)));
+    launch_take_w(o->s, o->a.as<float4>(), m, o->scan_w.as<float>());
+  }
   mark(1);
   // computeSpaciousness (odom.cc:981-1001): the median range is selected on
   // the device and copied to pinned memory, on the S2M context's stream (idle
@@ -1334,6 +1362,34 @@ gicp_status ddlo_odom_keyframe_points(const ddlo_odom* o, int k, float* xyz, siz
   return read_xyz(nullptr, kf.pts.as<float4>(), m, xyz);   // the null stream (idle: process waited for the keyframe)
 }
 
+gicp_status ddlo_odom_keyframe_points_xyzi(const ddlo_odom* o, int k, float* xyzi, size_t cap, size_t* n) {
+  if (!o || !n || (!xyzi && cap) || k < 0 || k >= (int)o->keyframes.size()) return fail(GICP_EINVAL, "invalid argument");
+  if (!o->inten_use) return fail(GICP_EINVAL, "the driver carries no intensity (ddlo_odom_set_intensity)");
+  const Keyframe& kf = *o->keyframes[k];
+  *n = (size_t)kf.n;
+  const size_t m = std::min(cap, (size_t)kf.n);
+  if (m == 0) return GICP_OK;
+  HIP_TRY(hipSetDevice(o->device));
+  HIP_TRY(hipMemcpy(xyzi, kf.pts.p, sizeof(float4) * m, hipMemcpyDeviceToHost));   // (idle, as ddlo_odom_keyframe_points)
+  return GICP_OK;
+}
+
+gicp_status ddlo_odom_set_intensity(ddlo_odom* o, int use, size_t offset_bytes) {
+  if (!o) return fail(GICP_EINVAL, "null handle");
+  if ((use != 0) != (o->inten_use != 0) && !o->keyframes.empty())
+    return fail(GICP_EINVAL, "intensity: a driver's keyframes either all have the channel or none do");
+  o->inten_use = use != 0;
+  o->inten_off = use ? offset_bytes : 0;
+  return GICP_OK;
+}
+
+gicp_status ddlo_odom_get_intensity(const ddlo_odom* o, int* use, size_t* offset_bytes) {
+  if (!o) return fail(GICP_EINVAL, "null handle");
+  if (use) *use = o->inten_use;
+  if (offset_bytes) *offset_bytes = o->inten_off;
+  return GICP_OK;
+}
+
 gicp_status ddlo_odom_keyframe(const ddlo_odom* o, int k, float pose7[7], size_t* npoints) {
   if (!o || k < 0 || k >= (int)o->keyframes.size()) return fail(GICP_EINVAL, "invalid keyframe index");
   const Keyframe& kf = *o->keyframes[k];
@@ -1407,8 +1463,10 @@ gicp_status ddlo_odom_get_downsampling(const ddlo_odom* o, int* use, int* row_st
 // ddlo_preprocess_ordered / ddlo_preprocess_downsampled (rows > 0: through the row/column filter)
 static gicp_status preprocess_entry(int device, const float* xyz, size_t n, size_t stride, int rows, int cols, int row_step,
                                     int col_step, double crop_size, double leaf, int order, float* out, size_t cap,
-                                    size_t* nout) {
+                                    size_t* nout, bool intensity = false, size_t ioff = 0) {
   if ((!xyz && n) || !nout || stride < 12 || stride % 4 || n > (size_t)INT32_MAX / 2) return fail(GICP_EINVAL, "invalid argument");
+  if (intensity && !intensity_offset_ok(ioff, stride))
+    return fail(GICP_EINVAL, "intensity offset: a multiple of 4, >= 12 and offset + 4 <= stride");
   if (order != DDLO_VOXEL_ORDER_INPUT && order != DDLO_VOXEL_ORDER_PCL) return fail(GICP_EINVAL, "unknown voxel order");
   ddlo_odom_params p;
   ddlo_odom_default_params(&p);
@@ -1417,14 +1475,17 @@ static gicp_status preprocess_entry(int device, const float* xyz, size_t n, size
   if (st) return st;
   std::unique_ptr<ddlo_odom, gicp_status (*)(ddlo_odom*)> guard(o, ddlo_odom_destroy);
   o->voxel_order = order;
+  o->inten_use = intensity;
+  o->inten_off = intensity ? ioff : 0;
   if (rows > 0) {
     st = ddlo_odom_set_downsampling(o, 1, row_step, col_step, rows, cols);
     if (st) return st;
   }
   *nout = 0;
   if (n == 0) return GICP_OK;
-  HIP_TRY(o->up.ensure((n - 1) * stride + 12));
-  HIP_TRY(hipMemcpyAsync(o->up.p, xyz, (n - 1) * stride + 12, hipMemcpyHostToDevice, o->s));
+  const size_t raw = raw_bytes(n, stride, o->inten_off);
+  HIP_TRY(o->up.ensure(raw));
+  HIP_TRY(hipMemcpyAsync(o->up.p, xyz, raw, hipMemcpyHostToDevice, o->s));
   HIP_TRY(o->a.ensure(sizeof(float4) * n));
   const int nr = pack_scan(o, (int)n, stride);
   int m = 0;
@@ -1433,9 +1494,20 @@ static gicp_status preprocess_entry(int device, const float* xyz, size_t n, size
   *nout = (size_t)m;
   if (out && m > 0) {
     if ((size_t)m > cap) return fail(GICP_EINVAL, "output capacity too small");
+    if (intensity) {   // 16 B per point, as they lie
+      HIP_TRY(hipMemcpyAsync(out, o->a.p, sizeof(float4) * (size_t)m, hipMemcpyDeviceToHost, o->s));
+      HIP_TRY(hipStreamSynchronize(o->s));
+      return GICP_OK;
+    }
     return read_xyz(o->s, o->a.as<float4>(), (size_t)m, out);
   }
   return GICP_OK;
+}
+
+gicp_status ddlo_preprocess_xyzi(int device, const float* pts, size_t n, size_t stride, size_t offset_bytes,
+                                 double crop_size, double leaf, int order, float* out_xyzi, size_t cap, size_t* n_out) {
+  return preprocess_entry(device, pts, n, stride, 0, 0, 1, 1, crop_size, leaf, order, out_xyzi, cap, n_out, true,
+                          offset_bytes);
 }
 
 gicp_status ddlo_preprocess_ordered(int device, const float* xyz, size_t n, size_t stride, double crop_size, double leaf,
@@ -1506,3 +1578,5 @@ gicp_status ddlo::odom_keyframe_dev(const ddlo_odom* o, int k, const float4** pt
   *stream = o->s;
   return GICP_OK;
 }
+
+bool ddlo::odom_has_intensity(const ddlo_odom* o) { return o && o->inten_use != 0; }

@@ -12,5 +12,7 @@ namespace ddlo {
 // filter; valid while the driver lives), its point count, the driver's
 // device and the stream its work is queued on.
 gicp_status odom_keyframe_dev(const ddlo_odom* o, int k, const float4** pts, int* n, int* device, hipStream_t* stream);
+// whether the keyframes' fourth lane holds the intensity (ddlo_odom_set_intensity), not 0
+bool odom_has_intensity(const ddlo_odom* o);
 
 }  // namespace ddlo

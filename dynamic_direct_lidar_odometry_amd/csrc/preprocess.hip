@@ -35,12 +35,16 @@ inline int cdiv_l(long a, long b) { return (int)((a + b - 1) / b); }
 }
 
 // ---- upload: strided host layout (e.g. 32-B PointXYZI) -> packed float4 ----
-__global__ __launch_bounds__(256) void k_pack4(const unsigned char* __restrict__ raw, size_t stride, int n,
+// INTEN (ddlo_intensity.h): w = the float ioff bytes into the record, its bits
+// as they are; else w = 0
+template <bool INTEN>
+__global__ __launch_bounds__(256) void k_pack4(const unsigned char* __restrict__ raw, size_t stride, int n, size_t ioff,
                                                float4* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float* p = reinterpret_cast<const float*>(raw + (size_t)i * stride);
-  out[i] = make_float4(p[0], p[1], p[2], 0.f);
+  const unsigned char* rec = raw + (size_t)i * stride;
+  const float* p = reinterpret_cast<const float*>(rec);
+  out[i] = make_float4(p[0], p[1], p[2], INTEN ? *reinterpret_cast<const float*>(rec + ioff) : 0.f);
 }
 
 // ---- upload through the row/column filter (odom.cc:445-455) ----
@@ -51,15 +55,17 @@ __global__ __launch_bounds__(256) void k_pack4(const unsigned char* __restrict__
 // (k / nc) row_step W + (k % nc) col_step, nc = ceil(W / col_step).  Ascending
 // k is ascending pixel index, so the pixels below n are a prefix of the
 // outputs; the host counts them (rowcol_count) and sizes the grid by it.
+template <bool INTEN>
 __global__ __launch_bounds__(256) void k_pack4_rowcol(const unsigned char* __restrict__ raw, size_t stride, int n, int W,
-                                                      int row_step, int col_step, int nc, int m,
+                                                      int row_step, int col_step, int nc, int m, size_t ioff,
                                                       float4* __restrict__ out) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= m) return;
   const long long pix = (long long)(k / nc) * row_step * W + (long long)(k % nc) * col_step;
   if (pix >= n) return;   // (never: m counts the pixels below n)
-  const float* p = reinterpret_cast<const float*>(raw + (size_t)pix * stride);
-  out[k] = make_float4(p[0], p[1], p[2], 0.f);
+  const unsigned char* rec = raw + (size_t)pix * stride;
+  const float* p = reinterpret_cast<const float*>(rec);
+  out[k] = make_float4(p[0], p[1], p[2], INTEN ? *reinterpret_cast<const float*>(rec + ioff) : 0.f);
 }
 
 // ---- crop box (negative: keep the points strictly outside [-s, s]^3) ----
@@ -200,21 +206,25 @@ __global__ void k_voxel_tail(const unsigned* __restrict__ uniq, int n, int* __re
 // AccumulatorXYZ).  The radix sort is stable, so that is the order its input
 // had: input order (DDLO_VOXEL_ORDER_INPUT), or the order std::sort's
 // partitions and heap sorts left (DDLO_VOXEL_ORDER_PCL, voxel_order.hip).
+// INTEN (AccumulatorIntensity): the fourth lane is summed beside the three, from
+// 0.f, in the same order, and divided by the same count; else out.w = 0.f.
+template <bool INTEN>
 __global__ __launch_bounds__(256) void k_voxel_centroids(const float4* __restrict__ in, const int* __restrict__ order,
                                                          const int* __restrict__ offsets, const int* __restrict__ counts,
                                                          int nruns, float4* __restrict__ out) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= nruns) return;
   const int o = offsets[r], c = counts[r];
-  float sx = 0.f, sy = 0.f, sz = 0.f;
+  float sx = 0.f, sy = 0.f, sz = 0.f, sw = 0.f;
   for (int k = 0; k < c; ++k) {
     const float4 p = in[order[o + k]];
     sx += p.x;
     sy += p.y;
     sz += p.z;
+    if (INTEN) sw += p.w;
   }
   const float fc = (float)c;
-  out[r] = make_float4(sx / fc, sy / fc, sz / fc, 0.f);
+  out[r] = make_float4(sx / fc, sy / fc, sz / fc, INTEN ? sw / fc : 0.f);
 }
 
 // ---- spaciousness: ranges ---------------------------------------------------
@@ -234,30 +244,44 @@ __global__ __launch_bounds__(256) void k_ranges(const float4* __restrict__ in, i
 struct T34 {
   float m[12];
 };
+// INTEN: pts is a registration context's sorted copy, whose w is a point index;
+// the intensity of output o comes from w_orig[o] (original order, k_take_w)
+template <bool INTEN>
 __global__ __launch_bounds__(256) void k_transform4(const float4* __restrict__ pts, const int* __restrict__ perm, int n,
-                                                    T34 T, float4* __restrict__ out) {
+                                                    T34 T, const float* __restrict__ w_orig, float4* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float4 p = pts[i];
   const float* m = T.m;
-  out[perm[i]] = make_float4((m[0] * p.x + m[1] * p.y) + (m[2] * p.z + m[3]),
-                             (m[4] * p.x + m[5] * p.y) + (m[6] * p.z + m[7]),
-                             (m[8] * p.x + m[9] * p.y) + (m[10] * p.z + m[11]), 0.f);
+  const int o = perm[i];
+  out[o] = make_float4((m[0] * p.x + m[1] * p.y) + (m[2] * p.z + m[3]),
+                       (m[4] * p.x + m[5] * p.y) + (m[6] * p.z + m[7]),
+                       (m[8] * p.x + m[9] * p.y) + (m[10] * p.z + m[11]), INTEN ? w_orig[o] : 0.f);
+}
+
+// the fourth lane of n points, one float each, in their order
+__global__ __launch_bounds__(256) void k_take_w(const float4* __restrict__ in, int n, float* __restrict__ w) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) w[i] = in[i].w;
 }
 
 // an organized sensor-frame scan (strided host layout) to the world frame, in
 // place order: out[i] = T * p(i) with k_transform4's operation order; a
 // non-finite point stays non-finite in every coordinate (0 * inf, NaN + x)
+// INTEN: w = the float ioff bytes into the record (a no-return pixel keeps its own too); else 0
+template <bool INTEN>
 __global__ __launch_bounds__(256) void k_transform_raw(const unsigned char* __restrict__ raw, size_t stride, int n, T34 T,
-                                                       float4* __restrict__ out) {
+                                                       size_t ioff, float4* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float* p = reinterpret_cast<const float*>(raw + (size_t)i * stride);
+  const unsigned char* rec = raw + (size_t)i * stride;
+  const float* p = reinterpret_cast<const float*>(rec);
   const float x = p[0], y = p[1], z = p[2];
+  const float w = INTEN ? *reinterpret_cast<const float*>(rec + ioff) : 0.f;
   const float* m = T.m;
   float4 r = make_float4((m[0] * x + m[1] * y) + (m[2] * z + m[3]), (m[4] * x + m[5] * y) + (m[6] * z + m[7]),
-                         (m[8] * x + m[9] * y) + (m[10] * z + m[11]), 0.f);
-  if (!(isfinite(x) && isfinite(y) && isfinite(z))) r = make_float4(NAN, NAN, NAN, 0.f);
+                         (m[8] * x + m[9] * y) + (m[10] * z + m[11]), w);
+  if (!(isfinite(x) && isfinite(y) && isfinite(z))) r = make_float4(NAN, NAN, NAN, w);
   out[i] = r;
 }
 
@@ -325,7 +349,7 @@ size_t voxel_tmp_bytes(int n) {
 // as std::sort's introsort loop leaves them (oscratch) before the stable sort;
 // the same launches follow, and no read-back is added.
 int voxel_grid(hipStream_t s, const float4* in, int n, float leaf, float4* out, int* scratch, void* tmp, size_t tmp_bytes,
-               int* count_host, float crop, int* pin, CropCentre centre, int order_mode, int* oscratch) {
+               int* count_host, float crop, int* pin, CropCentre centre, int order_mode, int* oscratch, bool intensity) {
   *count_host = 0;
   if (n <= 0) return 0;
   unsigned* keys = reinterpret_cast<unsigned*>(scratch);
@@ -371,7 +395,10 @@ int voxel_grid(hipStream_t s, const float4* in, int n, float leaf, float4* out, 
   // and form the last run; a real voxel index never reaches UINT_MAX here)
   int nruns = h[8];
   if (h[9] < n) nruns -= 1;
-  k_voxel_centroids<<<cdiv_l(std::max(nruns, 1), 256), 256, 0, s>>>(in, order, offsets, counts, nruns, out);
+  if (intensity)
+    k_voxel_centroids<true><<<cdiv_l(std::max(nruns, 1), 256), 256, 0, s>>>(in, order, offsets, counts, nruns, out);
+  else
+    k_voxel_centroids<false><<<cdiv_l(std::max(nruns, 1), 256), 256, 0, s>>>(in, order, offsets, counts, nruns, out);
   *count_host = nruns;
   return 0;
 }
@@ -502,8 +529,9 @@ size_t median_tmp_bytes(int n) {
   return sizeof(unsigned) * 3 * kMedBins;
 }
 
-void launch_pack4(hipStream_t s, const unsigned char* raw, size_t stride, int n, float4* out) {
-  k_pack4<<<cdiv_l(n, 256), 256, 0, s>>>(raw, stride, n, out);
+void launch_pack4(hipStream_t s, const unsigned char* raw, size_t stride, int n, float4* out, size_t ioff) {
+  if (ioff) k_pack4<true><<<cdiv_l(n, 256), 256, 0, s>>>(raw, stride, n, ioff, out);
+  else k_pack4<false><<<cdiv_l(n, 256), 256, 0, s>>>(raw, stride, n, 0, out);
 }
 long long rowcol_size(int rows, int cols, int row_step, int col_step) {
   return (long long)((rows + row_step - 1) / row_step) * ((cols + col_step - 1) / col_step);
@@ -519,22 +547,31 @@ int rowcol_count(int n, int rows, int cols, int row_step, int col_step) {
   return (int)cnt;   // <= n
 }
 int launch_pack4_rowcol(hipStream_t s, const unsigned char* raw, size_t stride, int n, int rows, int cols, int row_step,
-                        int col_step, float4* out) {
+                        int col_step, float4* out, size_t ioff) {
   const int m = rowcol_count(n, rows, cols, row_step, col_step);
-  if (m > 0)
-    k_pack4_rowcol<<<cdiv_l(m, 256), 256, 0, s>>>(raw, stride, n, cols, row_step, col_step,
-                                                  (cols + col_step - 1) / col_step, m, out);
+  const int nc = (cols + col_step - 1) / col_step;
+  if (m > 0 && ioff)
+    k_pack4_rowcol<true><<<cdiv_l(m, 256), 256, 0, s>>>(raw, stride, n, cols, row_step, col_step, nc, m, ioff, out);
+  else if (m > 0)
+    k_pack4_rowcol<false><<<cdiv_l(m, 256), 256, 0, s>>>(raw, stride, n, cols, row_step, col_step, nc, m, 0, out);
   return m;
 }
-void launch_transform4(hipStream_t s, const float4* pts, const int* perm, int n, const float* T12, float4* out) {
+void launch_transform4(hipStream_t s, const float4* pts, const int* perm, int n, const float* T12, float4* out,
+                       const float* w_orig) {
   T34 T;
   for (int e = 0; e < 12; ++e) T.m[e] = T12[e];
-  k_transform4<<<cdiv_l(n, 256), 256, 0, s>>>(pts, perm, n, T, out);
+  if (w_orig) k_transform4<true><<<cdiv_l(n, 256), 256, 0, s>>>(pts, perm, n, T, w_orig, out);
+  else k_transform4<false><<<cdiv_l(n, 256), 256, 0, s>>>(pts, perm, n, T, nullptr, out);
 }
-void launch_transform_raw(hipStream_t s, const unsigned char* raw, size_t stride, int n, const float* T12, float4* out) {
+void launch_take_w(hipStream_t s, const float4* in, int n, float* w) {
+  if (n > 0) k_take_w<<<cdiv_l(n, 256), 256, 0, s>>>(in, n, w);
+}
+void launch_transform_raw(hipStream_t s, const unsigned char* raw, size_t stride, int n, const float* T12, float4* out,
+                          size_t ioff) {
   T34 T;
   for (int e = 0; e < 12; ++e) T.m[e] = T12[e];
-  k_transform_raw<<<cdiv_l(n, 256), 256, 0, s>>>(raw, stride, n, T, out);
+  if (ioff) k_transform_raw<true><<<cdiv_l(n, 256), 256, 0, s>>>(raw, stride, n, T, ioff, out);
+  else k_transform_raw<false><<<cdiv_l(n, 256), 256, 0, s>>>(raw, stride, n, T, 0, out);
 }
 void launch_gather_cov6(hipStream_t s, const double* cov_sorted, const int* perm, int n, double* out) {
   k_gather_cov6<<<cdiv_l(n, 256), 256, 0, s>>>(cov_sorted, perm, n, out);

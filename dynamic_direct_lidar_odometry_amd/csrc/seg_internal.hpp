@@ -46,8 +46,10 @@ gicp_status seg_projection_resolve(ddlo_seg* s, const ddlo_seg_projection* proj,
 // Claim and fill: the n points in raw (device memory, stride bytes apart,
 // complete on st) into the segmentation's staged input (seg_stage_input),
 // moved by T; runs on st and waits for it.  *out: the counts.  proj: resolved.
+// ioff: where the float intensity sits in raw's records (the pixel's winner brings its own into the
+// staged input's w); 0: w = 0
 gicp_status seg_project_dev(ddlo_seg* s, hipStream_t st, const unsigned char* raw, size_t stride, int n, const float T[16],
-                            const ddlo_seg_projection& proj, ddlo_seg_projection_result* out);
+                            const ddlo_seg_projection& proj, ddlo_seg_projection_result* out, size_t ioff = 0);
 // after the seg_process_staged that followed seg_project_dev: the maps are
 // those of the handle's scan
 gicp_status seg_project_commit(ddlo_seg* s);

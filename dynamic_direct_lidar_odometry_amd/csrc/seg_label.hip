@@ -520,11 +520,15 @@ __global__ __launch_bounds__(kLblThreads) void k_lbl_avg(LblArgs a) {
   }
 }
 
+template <bool FLAGS>
 __global__ __launch_bounds__(kLblThreads) void k_lbl_drop(const int* __restrict__ ids, const int* __restrict__ off,
-                                                          const int* __restrict__ pix, float4* __restrict__ pts) {
+                                                          const int* __restrict__ pix, float4* __restrict__ pts,
+                                                          unsigned char* __restrict__ flags) {
   const int l = ids[blockIdx.y];
-  for (int i = off[l] + blockIdx.x * blockDim.x + threadIdx.x; i < off[l + 1]; i += gridDim.x * blockDim.x)
-    pts[pix[i]] = make_float4(NAN, NAN, NAN, kRemovedW);   // (a pixel named twice: the same bits)
+  for (int i = off[l] + blockIdx.x * blockDim.x + threadIdx.x; i < off[l + 1]; i += gridDim.x * blockDim.x) {
+    pts[pix[i]] = make_float4(NAN, NAN, NAN, FLAGS ? 0.f : kRemovedW);   // (a pixel named twice: the same bits)
+    if (FLAGS) flags[pix[i]] = 1;
+  }
 }
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
@@ -627,9 +631,11 @@ gicp_status label_device_run(hipStream_t s, const ddlo_seg_params& p, LabelDev& 
   return GICP_OK;
 }
 
-gicp_status label_device_drop(hipStream_t s, const LabelDev& w, const int* ids, int nids, float4* pts) {
+gicp_status label_device_drop(hipStream_t s, const LabelDev& w, const int* ids, int nids, float4* pts,
+                              unsigned char* flags) {
   if (nids <= 0) return GICP_OK;
-  k_lbl_drop<<<dim3(8, nids), kLblThreads, 0, s>>>(ids, w.off(), w.pixels(), pts);
+  if (flags) k_lbl_drop<true><<<dim3(8, nids), kLblThreads, 0, s>>>(ids, w.off(), w.pixels(), pts, flags);
+  else k_lbl_drop<false><<<dim3(8, nids), kLblThreads, 0, s>>>(ids, w.off(), w.pixels(), pts, nullptr);
   HIP_TRY(hipGetLastError());
   return GICP_OK;
 }

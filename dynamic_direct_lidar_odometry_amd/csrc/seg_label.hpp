@@ -84,7 +84,9 @@ gicp_status label_device_run(hipStream_t s, const ddlo_seg_params& p, LabelDev& 
 constexpr float kRemovedW = 1.f;
 
 // pts[pixel] = NaN (w = kRemovedW) for the pixels of the segments ids[0 .. nids) (device ints, each in 1 .. segments)
-gicp_status label_device_drop(hipStream_t s, const LabelDev& w, const int* ids, int nids, float4* pts);
+// flags (optional, seg_state.hpp's seg_removed_flags): the mark goes there, 1 per removed pixel, and w is left 0
+gicp_status label_device_drop(hipStream_t s, const LabelDev& w, const int* ids, int nids, float4* pts,
+                              unsigned char* flags = nullptr);
 
 gicp_status seg_check_params(const ddlo_seg_params* p);
 

@@ -104,9 +104,11 @@ struct ProjPose {
 };
 
 // partial[workgroup] = occupied pixels of the workgroup's 256
+// INTEN: the winner brings its own intensity (the float ioff bytes into its record) into w; else w = 0
+template <bool INTEN>
 __global__ __launch_bounds__(kProjThreads) void k_proj_fill(const int* __restrict__ winner, int npix,
                                                             const unsigned char* __restrict__ raw, size_t stride, int n,
-                                                            ProjPose T, float4* __restrict__ out,
+                                                            ProjPose T, size_t ioff, float4* __restrict__ out,
                                                             int* __restrict__ partial) {
   __shared__ int sh[kProjWaves];
   const int p = blockIdx.x * kProjThreads + threadIdx.x;
@@ -116,11 +118,13 @@ __global__ __launch_bounds__(kProjThreads) void k_proj_fill(const int* __restric
     float4 r = make_float4(NAN, NAN, NAN, 0.f);
     if ((unsigned)o < (unsigned)n) {   // (-1: no winner)
       occupied = true;
-      const float* q = reinterpret_cast<const float*>(raw + (size_t)o * stride);
+      const unsigned char* rec = raw + (size_t)o * stride;
+      const float* q = reinterpret_cast<const float*>(rec);
       const float x = q[0], y = q[1], z = q[2];
       const float* m = T.m;
       r = make_float4((m[0] * x + m[1] * y) + (m[2] * z + m[3]), (m[4] * x + m[5] * y) + (m[6] * z + m[7]),
-                      (m[8] * x + m[9] * y) + (m[10] * z + m[11]), 0.f);
+                      (m[8] * x + m[9] * y) + (m[10] * z + m[11]),
+                      INTEN ? *reinterpret_cast<const float*>(rec + ioff) : 0.f);
     }
     out[p] = r;
   }
@@ -243,7 +247,7 @@ gicp_status seg_projection_resolve(ddlo_seg* s, const ddlo_seg_projection* proj,
 }
 
 gicp_status seg_project_dev(ddlo_seg* s, hipStream_t st, const unsigned char* raw, size_t stride, int n, const float T[16],
-                            const ddlo_seg_projection& proj, ddlo_seg_projection_result* out) {
+                            const ddlo_seg_projection& proj, ddlo_seg_projection_result* out, size_t ioff) {
   if (!s || !T || (!raw && n) || n < 0) return fail(GICP_EINVAL, "invalid argument");
   if (gicp_status e = check_projection(proj)) return e;
   HIP_TRY(hipSetDevice(s->device));
@@ -276,7 +280,10 @@ gicp_status seg_project_dev(ddlo_seg* s, hipStream_t st, const unsigned char* ra
   if (n > 0)
     k_proj_claim<<<nwg_c, kProjThreads, 0, st>>>(raw, stride, n, m, npix, p->winner.as<int>(), p->pix.as<int>(),
                                                  claim_part);
-  k_proj_fill<<<nwg_f, kProjThreads, 0, st>>>(p->winner.as<int>(), npix, raw, stride, n, P, buf, fill_part);
+  if (ioff)
+    k_proj_fill<true><<<nwg_f, kProjThreads, 0, st>>>(p->winner.as<int>(), npix, raw, stride, n, P, ioff, buf, fill_part);
+  else
+    k_proj_fill<false><<<nwg_f, kProjThreads, 0, st>>>(p->winner.as<int>(), npix, raw, stride, n, P, 0, buf, fill_part);
   k_proj_sum<<<1, kProjThreads, 0, st>>>(claim_part, nwg_c, fill_part, nwg_f, p->counts.as<int>());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(p->pin.p, p->counts.p, sizeof(int) * 3, hipMemcpyDeviceToHost, st));
@@ -320,18 +327,21 @@ gicp_status ddlo_seg_process_cloud(ddlo_seg* s, const float* xyz, size_t n, size
                                    ddlo_seg_projection_result* proj_res) {
   if (!s || !T || (!xyz && n) || stride < 12 || stride % 4) return fail(GICP_EINVAL, "invalid argument");
   if (n > (size_t)INT32_MAX / 2) return fail(GICP_EINVAL, "cloud too large");
+  const size_t ioff = s->inten_use ? s->inten_off : 0;
+  if (ioff && (ioff % 4 || ioff < 12 || ioff + 4 > stride))
+    return fail(GICP_EINVAL, "intensity offset: a multiple of 4, >= 12 and offset + 4 <= stride");
   ddlo_seg_projection q;
   if (gicp_status st = seg_projection_resolve(s, proj, &q)) return st;
   HIP_TRY(hipSetDevice(s->device));
   SegProject* p = nullptr;
   if (gicp_status st = project_of(s, &p)) return st;
   if (n) {
-    const size_t raw_sz = (n - 1) * stride + 12;
+    const size_t raw_sz = (n - 1) * stride + std::max<size_t>(12, ioff ? ioff + 4 : 0);
     HIP_TRY(reserve(p->up, raw_sz));
     HIP_TRY(hipMemcpyAsync(p->up.p, xyz, raw_sz, hipMemcpyHostToDevice, s->s));
   }
   ddlo_seg_projection_result pr{};
-  if (gicp_status st = seg_project_dev(s, s->s, n ? p->up.as<unsigned char>() : nullptr, stride, (int)n, T, q, &pr))
+  if (gicp_status st = seg_project_dev(s, s->s, n ? p->up.as<unsigned char>() : nullptr, stride, (int)n, T, q, &pr, ioff))
     return st;
   if (gicp_status st = seg_process_staged(s, T, residual, res)) return st;
   if (gicp_status st = seg_project_commit(s)) return st;

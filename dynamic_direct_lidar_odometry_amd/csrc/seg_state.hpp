@@ -59,6 +59,13 @@ struct ddlo_seg {
   int ds_use = 0, ds_row = 1, ds_col = 1;
   ddlo::rt::DevBuf ds_part;
   bool ds_skipped = false;
+  // ddlo_seg_set_intensity: the static cloud's w is the channel, read from raw at inten_off (a scan of
+  // ddlo_seg_process) or at 12 (raw_staged: the float4 scan the driver or the projection staged).  The
+  // removal then cannot mark a pixel in w: with the row/column filter on it marks rm_flags instead.
+  int inten_use = 0;
+  size_t inten_off = 0, raw_inten_off = 0;   // raw_inten_off: what the scan in raw was uploaded with (0: x, y, z alone)
+  bool raw_staged = false;
+  ddlo::rt::DevBuf rm_flags;
   bool have_objects = false;         // objects holds the last scan's records
   std::vector<ddlo_seg_object> objects;   // every segment's record of the last scan (before the ratio test)
   // seg_csr: the last scan's segments are on the device (host labelling: dcsr
@@ -117,12 +124,22 @@ gicp_status seg_csr(ddlo_seg* s, SegCsr* out);
 
 // ddlo_seg_static_cloud* in three steps.  begin: the checks, the scratch, the
 // scan packed into s->f4.  Then the caller's removal: (NaN, NaN, NaN,
-// kRemovedW) over points of s->f4, on s->s.  finish: the row/column filter's
+// kRemovedW) over points of s->f4, on s->s; or, where seg_removed_flags(s) is
+// not null (cleared by begin), NaN over x, y, z and 1 in the pixel's flag.  finish: the row/column filter's
 // keyframe pass if it is on (ddlo_seg_set_downsampling), then the voxel filter
 // or the crop box into *pts / *count (valid until the next call on s);
 // complete when it returns.
 gicp_status seg_static_begin(ddlo_seg* s, const float centre[3], const float4** pts, int* count);
 gicp_status seg_static_finish(ddlo_seg* s, const float centre[3], double crop_size, double leaf, const float4** pts,
                               int* count);
+// The byte per pixel that marks a removed pixel for the row/column filter's keyframe pass when w is the
+// intensity and cannot; nullptr when the marker in w does (intensity off), or nobody reads it (filter off).
+inline unsigned char* seg_removed_flags(const ddlo_seg* s) {
+  return s->inten_use && s->ds_use ? s->rm_flags.as<unsigned char>() : nullptr;
+}
+// where the intensity of the scan in s->raw sits in its records; 0: not carried
+inline size_t seg_raw_intensity_offset(const ddlo_seg* s) {
+  return s->inten_use ? (s->raw_staged ? (size_t)12 : s->raw_inten_off) : 0;
+}
 
 }  // namespace ddlo

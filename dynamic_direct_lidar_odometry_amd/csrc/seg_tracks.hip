@@ -72,13 +72,18 @@ __global__ __launch_bounds__(kTrkThreads) void k_trk_gather(const TrkEntry* __re
 // stores the same bits, (NaN, NaN, NaN, kRemovedW: the removed flag of the
 // row/column filter's keyframe pass), so the result does not depend on which
 // store lands last.  Neither atomics nor a pass that removes duplicates.
+// FLAGS (seg_removed_flags: w is the intensity): the flag is a byte of the pixel's, 1 from every writer.
+template <bool FLAGS>
 __global__ __launch_bounds__(kTrkThreads) void k_trk_drop(const int2* __restrict__ ranges,
                                                           const int* __restrict__ pool, float4* __restrict__ pts,
-                                                          int npix) {
+                                                          int npix, unsigned char* __restrict__ flags) {
   const int2 r = ranges[blockIdx.y];   // (offset, length)
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < r.y; i += gridDim.x * blockDim.x) {
     const int p = pool[r.x + i];
-    if ((unsigned)p < (unsigned)npix) pts[p] = make_float4(NAN, NAN, NAN, kRemovedW);
+    if ((unsigned)p < (unsigned)npix) {
+      pts[p] = make_float4(NAN, NAN, NAN, FLAGS ? 0.f : kRemovedW);
+      if (FLAGS) flags[p] = 1;
+    }
   }
 }
 
@@ -218,8 +223,13 @@ gicp_status seg_static_cloud_tracks_dev(ddlo_seg* s, const int32_t* track_ids, s
     HIP_TRY(t->dtable.ensure(rb));
     std::memcpy(t->stage.p, ranges.data(), rb);
     HIP_TRY(hipMemcpyAsync(t->dtable.p, t->stage.p, rb, hipMemcpyHostToDevice, s->s));
-    k_trk_drop<<<dim3(chunks_for(maxlen), (unsigned)ranges.size()), kTrkThreads, 0, s->s>>>(
-        t->dtable.as<int2>(), t->pool[t->cur].as<int>(), s->f4.as<float4>(), (int)s->hn);
+    const dim3 grid(chunks_for(maxlen), (unsigned)ranges.size());
+    if (unsigned char* const flags = seg_removed_flags(s))
+      k_trk_drop<true><<<grid, kTrkThreads, 0, s->s>>>(t->dtable.as<int2>(), t->pool[t->cur].as<int>(),
+                                                        s->f4.as<float4>(), (int)s->hn, flags);
+    else
+      k_trk_drop<false><<<grid, kTrkThreads, 0, s->s>>>(t->dtable.as<int2>(), t->pool[t->cur].as<int>(),
+                                                         s->f4.as<float4>(), (int)s->hn, nullptr);
     HIP_TRY(hipGetLastError());
   }
   return seg_static_finish(s, centre, crop_size, leaf, pts, count);   // (waits for the stream)

@@ -437,9 +437,15 @@ __global__ __launch_bounds__(kObjThreads) void k_seg_objects(SegObjArgs a) {
 // w = kRemovedW marks the pixel as removed (a no-return pixel is NaN with the
 // w = 0 the pack gave it): the row/column filter's keyframe pass tells them
 // apart.  A pixel named twice gets the same bits twice.
-__global__ __launch_bounds__(256) void k_static_drop(const int* __restrict__ pix, int m, float4* __restrict__ pts) {
+// FLAGS (ddlo_seg_set_intensity with the row/column filter on: w is the channel, of a kept pixel any
+// value and of a no-return pixel too): the mark is a byte of the pixel's instead, and w is left 0.
+template <bool FLAGS>
+__global__ __launch_bounds__(256) void k_static_drop(const int* __restrict__ pix, int m, float4* __restrict__ pts,
+                                                     unsigned char* __restrict__ flags) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < m) pts[pix[j]] = make_float4(NAN, NAN, NAN, kRemovedW);
+  if (j >= m) return;
+  pts[pix[j]] = make_float4(NAN, NAN, NAN, FLAGS ? 0.f : kRemovedW);
+  if (FLAGS) flags[pix[j]] = 1;
 }
 
 // ---- the row/column filter's keyframe pass (odom.cc:902-906) ----------------
@@ -805,9 +811,12 @@ static gicp_status seg_run(ddlo_seg* o, const float* xyz_t, size_t stride, const
   o->have_objects = false;
   o->csr_ready = o->csr_len_ready = false;
   ++o->scan_serial;
-  const size_t raw_sz = (n - 1) * stride + 12;
+  const size_t ioff = xyz_t && o->inten_use ? o->inten_off : 0;
+  const size_t raw_sz = (n - 1) * stride + std::max<size_t>(12, ioff ? ioff + 4 : 0);
   HIP_TRY(o->raw.ensure(raw_sz));
   o->raw_stride = stride;
+  o->raw_staged = !xyz_t;
+  o->raw_inten_off = ioff;
   HIP_TRY(o->range.ensure(sizeof(float) * n));
   HIP_TRY(o->ground.ensure(n));
   HIP_TRY(o->label.ensure(sizeof(int) * n));
@@ -855,6 +864,8 @@ extern "C" {
 gicp_status ddlo_seg_process(ddlo_seg* o, const float* xyz_t, size_t stride, const float T[16], const float* residual,
                              ddlo_seg_result* res) {
   if (!o || !xyz_t || !T || stride < 12 || stride % 4) return fail(GICP_EINVAL, "invalid argument");
+  if (o->inten_use && (o->inten_off % 4 || o->inten_off < 12 || o->inten_off + 4 > stride))
+    return fail(GICP_EINVAL, "intensity offset: a multiple of 4, >= 12 and offset + 4 <= stride");
   return seg_run(o, xyz_t, stride, T, residual, res);
 }
 
@@ -1044,7 +1055,11 @@ gicp_status seg_static_begin(ddlo_seg* o, const float centre[3], const float4** 
   HIP_TRY(o->cubtmp.ensure(std::max(crop_box_tmp_bytes(n), voxel_tmp_bytes(n))));
   if (o->voxel_order != 0) HIP_TRY(o->voscratch.ensure(sizeof(int) * voxel_order_scratch_ints(n)));
   if (o->ds_use) HIP_TRY(o->ds_part.ensure(sizeof(int) * downsample_scratch_ints(n)));
-  launch_pack4(o->s, o->raw.as<unsigned char>(), o->raw_stride, n, o->f4.as<float4>());
+  launch_pack4(o->s, o->raw.as<unsigned char>(), o->raw_stride, n, o->f4.as<float4>(), seg_raw_intensity_offset(o));
+  if (o->inten_use && o->ds_use) {
+    HIP_TRY(o->rm_flags.ensure((size_t)n));
+    HIP_TRY(hipMemsetAsync(o->rm_flags.p, 0, (size_t)n, o->s));
+  }
   return GICP_OK;
 }
 
@@ -1060,14 +1075,14 @@ gicp_status seg_static_finish(ddlo_seg* o, const float centre[3], double crop_si
     // the row/column filter's keyframe pass, between the removal and the crop: NaN over the points
     // that leave.  Its |S| <= n' decision is taken on the device; the bit comes back in stream order
     // with the filters' count below, which is waited for anyway.
-    const int* ctrl = launch_downsample_keep(o->s, nullptr, o->f4.as<float4>(), n, o->p.rows, o->p.cols, o->ds_row,
+    const int* ctrl = launch_downsample_keep(o->s, seg_removed_flags(o), o->f4.as<float4>(), n, o->p.rows, o->p.cols, o->ds_row,
                                              o->ds_col, nullptr, o->ds_part.as<int>());
     HIP_TRY(hipMemcpyAsync(skipped, ctrl, sizeof(int), hipMemcpyDeviceToHost, o->s));
   }
   if (leaf > 0) {   // the crop box folded into the voxel pass (as the driver's preprocessing does)
     if (voxel_grid(o->s, o->f4.as<float4>(), n, (float)leaf, o->f4b.as<float4>(), o->vscratch.as<int>(), o->cubtmp.p,
                    o->cubtmp.bytes, &m, crop ? (float)crop_size : 0.f, o->cnt_pin.as<int>(), cc, o->voxel_order,
-                   o->voscratch.as<int>()))
+                   o->voscratch.as<int>(), o->inten_use != 0))
       return fail(GICP_EHIP, "voxel filter scratch too small");
   }
   if (m < 0) {   // no voxel filter, or its grid overflows (the reference then keeps the cloud as it is)
@@ -1105,7 +1120,9 @@ gicp_status seg_static_cloud_dev(ddlo_seg* o, const int32_t* remove_ids, size_t 
     std::memcpy(drop, remove_ids, sizeof(int) * n_remove);
     HIP_TRY(rt::grow(o->dids, sizeof(int) * n_remove, o->s));
     HIP_TRY(hipMemcpyAsync(o->dids.p, drop, sizeof(int) * n_remove, hipMemcpyHostToDevice, o->s));
-    if (gicp_status st = label_device_drop(o->s, o->ldev, o->dids.as<int>(), (int)n_remove, o->f4.as<float4>())) return st;
+    if (gicp_status st = label_device_drop(o->s, o->ldev, o->dids.as<int>(), (int)n_remove, o->f4.as<float4>(),
+                                           seg_removed_flags(o)))
+      return st;
   }
   if (ndrop) {
     size_t w = 0;
@@ -1116,7 +1133,11 @@ gicp_status seg_static_cloud_dev(ddlo_seg* o, const int32_t* remove_ids, size_t 
     }
     HIP_TRY(o->ddrop.ensure(sizeof(int) * ndrop));
     HIP_TRY(hipMemcpyAsync(o->ddrop.p, drop, sizeof(int) * ndrop, hipMemcpyHostToDevice, o->s));
-    k_static_drop<<<cdiv_s((long)ndrop, 256), 256, 0, o->s>>>(o->ddrop.as<int>(), (int)ndrop, o->f4.as<float4>());
+    if (unsigned char* const flags = seg_removed_flags(o))
+      k_static_drop<true><<<cdiv_s((long)ndrop, 256), 256, 0, o->s>>>(o->ddrop.as<int>(), (int)ndrop, o->f4.as<float4>(), flags);
+    else
+      k_static_drop<false><<<cdiv_s((long)ndrop, 256), 256, 0, o->s>>>(o->ddrop.as<int>(), (int)ndrop, o->f4.as<float4>(),
+                                                                       nullptr);
   }
   HIP_TRY(hipGetLastError());
   return seg_static_finish(o, centre, crop_size, leaf, pts, count);
@@ -1185,6 +1206,36 @@ gicp_status ddlo_seg_static_cloud(ddlo_seg* o, const int32_t* remove_ids, size_t
   if (!out || m == 0) return GICP_OK;
   if ((size_t)m > cap) return fail(GICP_EINVAL, "output capacity too small");
   return rt::read_xyz(o->s, pts, (size_t)m, out);
+}
+
+gicp_status ddlo_seg_static_cloud_xyzi(ddlo_seg* o, const int32_t* remove_ids, size_t n_remove, const float centre[3],
+                                       double crop_size, double leaf, float* out_xyzi, size_t cap, size_t* nout) {
+  if (!o || !nout || (!out_xyzi && cap)) return fail(GICP_EINVAL, "invalid argument");
+  if (!o->inten_use) return fail(GICP_EINVAL, "the segmentation carries no intensity (ddlo_seg_set_intensity)");
+  const float4* pts = nullptr;
+  int m = 0;
+  gicp_status st = seg_static_cloud_dev(o, remove_ids, n_remove, centre, crop_size, leaf, &pts, &m);
+  if (st) return st;
+  *nout = (size_t)m;
+  if (!out_xyzi || m == 0) return GICP_OK;
+  if ((size_t)m > cap) return fail(GICP_EINVAL, "output capacity too small");
+  HIP_TRY(hipMemcpyAsync(out_xyzi, pts, sizeof(float4) * (size_t)m, hipMemcpyDeviceToHost, o->s));
+  HIP_TRY(hipStreamSynchronize(o->s));
+  return GICP_OK;
+}
+
+gicp_status ddlo_seg_set_intensity(ddlo_seg* o, int use, size_t offset_bytes) {
+  if (!o) return fail(GICP_EINVAL, "null handle");
+  o->inten_use = use != 0;
+  o->inten_off = use ? offset_bytes : 0;
+  return GICP_OK;
+}
+
+gicp_status ddlo_seg_get_intensity(const ddlo_seg* o, int* use, size_t* offset_bytes) {
+  if (!o) return fail(GICP_EINVAL, "null handle");
+  if (use) *use = o->inten_use;
+  if (offset_bytes) *offset_bytes = o->inten_off;
+  return GICP_OK;
 }
 
 }  // extern "C"

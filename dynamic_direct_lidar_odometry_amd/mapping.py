@@ -56,6 +56,10 @@ def _lib():
             "ddlo_map_size": (I, [P, C.POINTER(S)]),
             "ddlo_map_points": (I, [P, D, P, S, C.POINTER(S)]),
             "ddlo_map_save_pcd": (I, [P, C.c_char_p, D]),
+            "ddlo_map_set_intensity": (I, [P, I]),
+            "ddlo_map_get_intensity": (I, [P, C.POINTER(I)]),
+            "ddlo_map_add_keyframe_xyzi": (I, [P, P, S, S, S, C.POINTER(S)]),
+            "ddlo_map_points_xyzi": (I, [P, D, P, S, C.POINTER(S)]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -129,8 +133,28 @@ class Map:
         except Exception:
             pass
 
-    def add_keyframe(self, points) -> int:
-        """keyframeCB for world-frame points (n, 3); returns the number of points appended."""
+    def set_intensity(self, use) -> None:
+        """ddlo_map_set_intensity: whether the map carries the intensity channel; only while it is empty."""
+        _check(self.L.ddlo_map_set_intensity(self.h, int(bool(use))))
+
+    @property
+    def intensity(self) -> bool:
+        u = C.c_int()
+        _check(self.L.ddlo_map_get_intensity(self.h, C.byref(u)))
+        return bool(u.value)
+
+    def add_keyframe(self, points, intensity_offset: int | None = None) -> int:
+        """keyframeCB for world-frame points (n, 3); returns the number of points appended.
+        intensity_offset (a map with set_intensity on): ddlo_map_add_keyframe_xyzi on (n, c) float32 rows
+        whose intensity is the float at that byte offset (12 for x y z i rows)."""
+        if intensity_offset is not None:
+            a = np.ascontiguousarray(points, np.float32)
+            if a.ndim != 2 or a.shape[1] < 3:
+                raise ValueError("points must be (n, >=3)")
+            added = C.c_size_t()
+            _check(self.L.ddlo_map_add_keyframe_xyzi(self.h, _ptr(a) if a.shape[0] else None, a.shape[0],
+                                                     a.shape[1] * 4, int(intensity_offset), C.byref(added)))
+            return added.value
         a = np.ascontiguousarray(np.asarray(points, dtype=np.float32).reshape(-1, 3))
         added = C.c_size_t()
         _check(self.L.ddlo_map_add_keyframe(self.h, _ptr(a) if a.shape[0] else None, a.shape[0], 12, C.byref(added)))
@@ -154,13 +178,19 @@ class Map:
         _check(self.L.ddlo_map_size(self.h, C.byref(n)))
         return n.value
 
-    def points(self, leaf: float = 0.0) -> np.ndarray:
-        """The map (n, 3) float32; leaf > 0: savePcd's voxelised copy, the map unchanged."""
+    def points(self, leaf: float = 0.0, intensity: bool = False) -> np.ndarray:
+        """The map (n, 3) float32; leaf > 0: savePcd's voxelised copy, the map unchanged.
+        intensity=True (a map with set_intensity on): (n, 4), ddlo_map_points_xyzi."""
+        if intensity:
+            out = np.zeros((max(len(self), 1), 4), np.float32)
+            n = C.c_size_t()
+            _check(self.L.ddlo_map_points_xyzi(self.h, float(leaf), _ptr(out), out.shape[0], C.byref(n)))
+            return out[:n.value]
         out = np.zeros((max(len(self), 1), 3), np.float32)      # the voxelised copy is never larger
         n = C.c_size_t()
         _check(self.L.ddlo_map_points(self.h, float(leaf), _ptr(out), out.shape[0], C.byref(n)))
         return out[:n.value]
 
     def save_pcd(self, path, leaf: float = 0.0) -> None:
-        """savePcd: binary PCD v0.7 with FIELDS x y z."""
+        """savePcd: binary PCD v0.7 with FIELDS x y z (a map with intensity: x y z intensity)."""
         _check(self.L.ddlo_map_save_pcd(self.h, os.fsencode(path), float(leaf)))

@@ -123,6 +123,10 @@ def _lib():
             "ddlo_odom_get_downsampling": (I, [P] + [C.POINTER(I)] * 5),
             "ddlo_preprocess_downsampled": (I, [I, P, S, S, I, I, I, I, D, D, I, P, S, C.POINTER(S)]),
             "ddlo_debug_downsample_keep": (I, [I, P, S, I, I, I, I, P, C.POINTER(I)]),
+            "ddlo_odom_set_intensity": (I, [P, I, S]),
+            "ddlo_odom_get_intensity": (I, [P, C.POINTER(I), C.POINTER(S)]),
+            "ddlo_odom_keyframe_points_xyzi": (I, [P, I, P, S, C.POINTER(S)]),
+            "ddlo_preprocess_xyzi": (I, [I, P, S, S, S, D, D, I, P, S, C.POINTER(S)]),
             "ddlo_median_range": (I, [I, P, S, S, C.POINTER(C.c_float)]),
             "ddlo_convex_hull": (I, [P, I, P, I, C.POINTER(I)]),
             "ddlo_concave_hull": (I, [P, I, D, P, I, C.POINTER(I)]),
@@ -168,6 +172,7 @@ class Odometry:
     def __init__(self, device: int = 0, params: OdomParams | None = None):
         self.L = _lib()
         self.h = C.c_void_p()
+        self._intensity = False     # set_intensity's flag, kept here so that process() asks nothing per frame
         _check(self.L.ddlo_odom_create(device, C.byref(params) if params is not None else None, C.byref(self.h)))
 
     def close(self):
@@ -207,9 +212,30 @@ class Odometry:
         _check(self.L.ddlo_odom_get_downsampling(self.h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
+    def set_intensity(self, use, offset_bytes: int = 12):
+        """ddlo_odom_set_intensity: carry the float at offset_bytes of every point record (12: packed
+        x y z i rows; 16: pcl::PointXYZI) through the filters into the keyframes.  With it on, process()
+        takes (n, >= 4) float32 rows, and the row size is the stride.  Not after the first keyframe."""
+        _check(self.L.ddlo_odom_set_intensity(self.h, int(bool(use)), int(offset_bytes)))
+        self._intensity = bool(use)
+
+    @property
+    def intensity(self):
+        """(use, offset_bytes) as set."""
+        u, off = C.c_int(), C.c_size_t()
+        _check(self.L.ddlo_odom_get_intensity(self.h, C.byref(u), C.byref(off)))
+        return bool(u.value), off.value
+
     def process(self, points) -> OdomResult:
-        a = _xyz(points)
         r = OdomResult()
+        if self._intensity:
+            a = np.ascontiguousarray(points, np.float32)
+            if a.ndim != 2 or a.shape[1] < 4:
+                raise ValueError("with intensity on, points must be (n, >=4)")
+            _check(self.L.ddlo_odom_process(self.h, _ptr(a) if a.shape[0] else None, a.shape[0], a.shape[1] * 4,
+                                            C.byref(r)))
+            return r
+        a = _xyz(points)
         _check(self.L.ddlo_odom_process(self.h, _ptr(a), a.shape[0], 12, C.byref(r)))
         return r
 
@@ -317,9 +343,15 @@ class Odometry:
         _check(self.L.ddlo_odom_classify(seg.h, tracker.h, C.byref(c)))
         return c
 
-    def keyframe_points(self, k: int) -> np.ndarray:
-        """World-frame points of keyframe k (after the submap voxel filter), (n, 3) float32."""
+    def keyframe_points(self, k: int, intensity: bool = False) -> np.ndarray:
+        """World-frame points of keyframe k (after the submap voxel filter), (n, 3) float32; intensity=True
+        (a driver with set_intensity on): (n, 4), the same rows with their intensity."""
         n = C.c_size_t()
+        if intensity:
+            _check(self.L.ddlo_odom_keyframe_points_xyzi(self.h, k, None, 0, C.byref(n)))
+            out = np.zeros((max(n.value, 1), 4), np.float32)
+            _check(self.L.ddlo_odom_keyframe_points_xyzi(self.h, k, _ptr(out), out.shape[0], C.byref(n)))
+            return out[:n.value]
         _check(self.L.ddlo_odom_keyframe_points(self.h, k, None, 0, C.byref(n)))
         out = np.zeros((max(n.value, 1), 3), np.float32)
         _check(self.L.ddlo_odom_keyframe_points(self.h, k, _ptr(out), out.shape[0], C.byref(n)))
@@ -340,9 +372,21 @@ class Odometry:
 
 
 def preprocess(points, crop_size: float = 0.0, leaf: float = 0.0, device: int = 0,
-               order: int = VOXEL_ORDER_INPUT) -> np.ndarray:
+               order: int = VOXEL_ORDER_INPUT, intensity_offset: int | None = None) -> np.ndarray:
     """Device crop box (points inside [-s, s]^3 removed) then voxel filter.  order: the voxel filter sums
-    each voxel's points in input order (VOXEL_ORDER_INPUT) or in pcl::VoxelGrid's (VOXEL_ORDER_PCL)."""
+    each voxel's points in input order (VOXEL_ORDER_INPUT) or in pcl::VoxelGrid's (VOXEL_ORDER_PCL).
+    intensity_offset: ddlo_preprocess_xyzi on (n, c) float32 rows (the stride is the row size) whose
+    intensity is the float at that byte offset; returns (m, 4): x, y, z, intensity."""
+    if intensity_offset is not None:
+        a = np.ascontiguousarray(points, np.float32)
+        if a.ndim != 2 or a.shape[1] < 3:
+            raise ValueError("points must be (n, >=3)")
+        out = np.zeros((max(a.shape[0], 1), 4), np.float32)
+        n = C.c_size_t()
+        _check(_lib().ddlo_preprocess_xyzi(device, _ptr(a) if a.shape[0] else None, a.shape[0], a.shape[1] * 4,
+                                           int(intensity_offset), float(crop_size), float(leaf), int(order),
+                                           _ptr(out), out.shape[0], C.byref(n)))
+        return out[:n.value]
     a = _xyz(points)
     out = np.zeros((max(a.shape[0], 1), 3), np.float32)
     n = C.c_size_t()

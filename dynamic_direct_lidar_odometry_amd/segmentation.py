@@ -153,6 +153,9 @@ def _lib():
             "ddlo_seg_objects": (I, [P, F, P, S, C.POINTER(S)]),
             "ddlo_seg_objects_from": (I, [I, P, S, I, I, P, P, S, F, P, S, C.POINTER(S)]),
             "ddlo_seg_static_cloud": (I, [P, P, S, P, C.c_double, C.c_double, P, S, C.POINTER(S)]),
+            "ddlo_seg_static_cloud_xyzi": (I, [P, P, S, P, C.c_double, C.c_double, P, S, C.POINTER(S)]),
+            "ddlo_seg_set_intensity": (I, [P, I, S]),
+            "ddlo_seg_get_intensity": (I, [P, C.POINTER(I), C.POINTER(S)]),
             "ddlo_seg_tracks_sync": (I, [P, P, P, S, P, S]),
             "ddlo_seg_static_cloud_tracks": (I, [P, P, S, P, C.c_double, C.c_double, P, S, C.POINTER(S)]),
             "ddlo_seg_track_indices": (I, [P, C.c_int32, P, S, C.POINTER(S)]),
@@ -298,6 +301,19 @@ class Segmentation:
         _check(self.L.ddlo_seg_get_voxel_order(self.h, C.byref(m)))
         return m.value
 
+    def set_intensity(self, use, offset_bytes: int = 12):
+        """ddlo_seg_set_intensity: static_cloud carries the float at offset_bytes of the records process() /
+        process_cloud() are given (from the next scan on), or the channel of the scan an Odometry with
+        set_intensity on staged."""
+        _check(self.L.ddlo_seg_set_intensity(self.h, int(bool(use)), int(offset_bytes)))
+
+    @property
+    def intensity(self):
+        """(use, offset_bytes) as set."""
+        u, off = C.c_int(), C.c_size_t()
+        _check(self.L.ddlo_seg_get_intensity(self.h, C.byref(u), C.byref(off)))
+        return bool(u.value), off.value
+
     def set_downsampling(self, use, row_step: int, col_step: int):
         """ddlo_seg_set_downsampling: the row/column filter's keyframe pass inside static_cloud /
         static_cloud_tracks, between the removal and the crop, from the next call on."""
@@ -441,13 +457,20 @@ class Segmentation:
             _check(self.L.ddlo_seg_objects(self.h, float(max_dim_ratio), _ptr(out), out.size, C.byref(n)))
         return out
 
-    def static_cloud(self, remove_ids=(), centre=(0.0, 0.0, 0.0), crop_size: float = 0.0, leaf: float = 0.0):
+    def static_cloud(self, remove_ids=(), centre=(0.0, 0.0, 0.0), crop_size: float = 0.0, leaf: float = 0.0,
+                     intensity: bool = False):
         """applySegmentation's tail (odom.cc:887-918): the last scan without the pixels of the segments in
-        remove_ids, cropped around centre and voxel-filtered; (m, 3) float32."""
+        remove_ids, cropped around centre and voxel-filtered; (m, 3) float32.  intensity=True (a handle with
+        set_intensity on): (m, 4), ddlo_seg_static_cloud_xyzi."""
         ids = np.ascontiguousarray(remove_ids, np.int32).reshape(-1)
         c = np.ascontiguousarray(centre, np.float32).reshape(3)
         n = C.c_size_t()
         args = (self.h, _ptr(ids) if ids.size else None, ids.size, _ptr(c), float(crop_size), float(leaf))
+        if intensity:
+            _check(self.L.ddlo_seg_static_cloud_xyzi(*args, None, 0, C.byref(n)))
+            out = np.zeros((max(n.value, 1), 4), np.float32)
+            _check(self.L.ddlo_seg_static_cloud_xyzi(*args, _ptr(out), out.shape[0], C.byref(n)))
+            return out[:n.value]
         _check(self.L.ddlo_seg_static_cloud(*args, None, 0, C.byref(n)))
         out = np.zeros((max(n.value, 1), 3), np.float32)
         _check(self.L.ddlo_seg_static_cloud(*args, _ptr(out), out.shape[0], C.byref(n)))

@@ -21,7 +21,8 @@
  *   - the yaw rotation is undone with the transpose of the rotation (the
  *     reference inverts the affine matrix with Eigen's general inverse), so a
  *     point within float rounding of a rotated box's face is not pinned;
- *   - no intensity is carried (nowhere in this project).
+ *   - intensity is carried only on request (ddlo_map_set_intensity,
+ *     ddlo_intensity.h); by default the map holds x, y, z alone.
  *
  * Not restated: ROS publishing (publishTimerCB), the tracker that produces
  * the boxes.
@@ -30,6 +31,7 @@
 #define DDLO_MAP_H
 
 #include "ddlo_odom.h"
+#include "ddlo_intensity.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -291,4 +291,7 @@ gicp_status ddlo_concave_hull(const float* xyz, int n, double alpha, int32_t* id
 }
 #endif
 
+/* the opt-in intensity channel: ddlo_odom_set_intensity, ddlo_odom_keyframe_points_xyzi, ddlo_preprocess_xyzi */
+#include "ddlo_intensity.h"
+
 #endif /* DDLO_ODOM_H */
