@@ -10,7 +10,7 @@ LIBDIR := $(PKG)/_lib
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function
 # the hot path, one file per stage (K1 .. K6), then the other translation units
 STAGES := index_build covariance corr_search moments outputs
-SRCS := $(STAGES) knn_tasks nftree cellgrid tietree cloud cellgrid_host align comm capi capi_debug preprocess voxel_order odom segment seg_label seg_tracks seg_classes seg_project map track
+SRCS := $(STAGES) knn_tasks nftree cellgrid tietree cloud cellgrid_host align comm capi capi_debug preprocess voxel_order deskew odom segment seg_label seg_tracks seg_classes seg_project map track
 # host-only translation units (.cpp), compiled as the others are so that they share runtime.hpp
 HOST_SRCS := eval
 OBJS := $(SRCS:%=$(LIBDIR)/%.o) $(HOST_SRCS:%=$(LIBDIR)/%.o)

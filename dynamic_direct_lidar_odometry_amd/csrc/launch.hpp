@@ -178,4 +178,19 @@ void launch_transform_raw(hipStream_t s, const unsigned char* raw, size_t stride
                           size_t ioff = 0);
 void launch_gather_cov6(hipStream_t s, const double* cov_sorted, const int* perm, int n, double* out);
 
+// deskew.hip (ddlo_deskew.h): a scan's twist as the kernel takes it, by value
+struct DeskewTwist {
+  double theta, k[3], t[3], ref_time, period;
+};
+// theta, k = omega / theta (0 when theta == 0) and the rest into *w; false for the identity twist (launch nothing)
+bool deskew_twist(const double* omega, const double* t, double ref_time, double period, DeskewTwist* w);
+// the header's rules for the time field's place in a record; nullptr when they hold.  inten: the
+// intensity channel is on, at ioff
+const char* deskew_field_error(int time_type, size_t toff, size_t stride, bool inten, size_t ioff);
+// the split log of inv(T_a) * T_b (row-major float poses, taken in double): the constant-velocity prediction
+void deskew_between(const float* Ta, const float* Tb, double* omega, double* t);
+// the in-place pass over n uploaded records: x, y, z of every point with finite coordinates and time
+void launch_deskew(hipStream_t s, unsigned char* raw, size_t stride, int n, int time_type, size_t toff,
+                   const DeskewTwist& w);
+
 }  // namespace ddlo

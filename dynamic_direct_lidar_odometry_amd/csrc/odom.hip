@@ -478,6 +478,16 @@ struct ddlo_odom {
   int inten_use = 0;
   size_t inten_off = 0;
   DevBuf scan_w;
+  // ddlo_odom_set_deskew (ddlo_deskew.h): the setting; the caller's twist for the next uploaded scan;
+  // what the last scan got (source 0 none, 1 predicted, 2 the caller's); the last two poses T_ of
+  // FIRST / TRACKED frames, [1] the newer, for the constant-velocity prediction
+  ddlo_deskew_params dk{0, DDLO_TIME_F32_S, 12, 0.0, 0.1};
+  bool dk_pending = false;
+  double dk_pend_w[3] = {0, 0, 0}, dk_pend_t[3] = {0, 0, 0};
+  int dk_source = 0;
+  double dk_w[3] = {0, 0, 0}, dk_t[3] = {0, 0, 0};
+  int dk_poses = 0;
+  float dk_T[2][16];
   // pinned host memory: [0] the median range of the current scan, [4..19] the
   // voxel / crop count read-back (int)
   PinBuf median_pin;
@@ -882,8 +892,37 @@ void copy_pose(const float* T, float* out) { std::memcpy(out, T, sizeof(float) *
 
 // ddlo_intensity.h's rules for the place of the intensity in a record
 bool intensity_offset_ok(size_t off, size_t stride) { return off % 4 == 0 && off >= 12 && off + 4 <= stride; }
-// the bytes of n records that are read: x, y, z of the last one, and its intensity if that is on
-size_t raw_bytes(size_t n, size_t stride, size_t ioff) { return (n - 1) * stride + std::max<size_t>(12, ioff ? ioff + 4 : 0); }
+// the bytes of n records that are read: x, y, z of the last one, its intensity if that is on, and
+// its time (tend = the byte after the time field) if deskew is on
+size_t raw_bytes(size_t n, size_t stride, size_t ioff, size_t tend = 0) {
+  return (n - 1) * stride + std::max(std::max<size_t>(12, ioff ? ioff + 4 : 0), tend);
+}
+
+// ddlo_deskew.h: the twist of the scan just uploaded into o->up (the caller's, for this scan only, or
+// the prediction from the last two poses) and the in-place pass, on o->s behind the copy
+void deskew_upload(ddlo_odom* o, int n, size_t stride) {
+  if (o->dk_pending) {
+    o->dk_pending = false;
+    std::memcpy(o->dk_w, o->dk_pend_w, sizeof(o->dk_w));
+    std::memcpy(o->dk_t, o->dk_pend_t, sizeof(o->dk_t));
+    o->dk_source = 2;
+  } else if (o->dk_poses >= 2) {
+    deskew_between(o->dk_T[0], o->dk_T[1], o->dk_w, o->dk_t);
+    o->dk_source = 1;
+  }
+  DeskewTwist w;
+  if (o->dk_source && deskew_twist(o->dk_w, o->dk_t, o->dk.ref_time, o->dk.period, &w))
+    launch_deskew(o->s, o->up.as<unsigned char>(), stride, n, o->dk.time_type, o->dk.time_offset_bytes, w);
+  else
+    o->dk_source = 0;
+}
+
+// a pose T_ the driver produced (FIRST: the identity; TRACKED) joins the prediction's history
+void deskew_push_pose(ddlo_odom* o) {
+  std::memcpy(o->dk_T[0], o->dk_T[1], sizeof(float) * 16);
+  std::memcpy(o->dk_T[1], o->T, sizeof(float) * 16);
+  o->dk_poses = std::min(o->dk_poses + 1, 2);
+}
 
 // the n uploaded points of o->up into o->a as float4; returns how many.  With
 // the row/column filter on: only the pixels of S below n, ascending, unless
@@ -1027,6 +1066,9 @@ static gicp_status process_scan(ddlo_odom* o, const float* xyz, size_t n, size_t
   if (n > (size_t)INT32_MAX / 2) return fail(GICP_EINVAL, "scan too large");
   if (o->inten_use && !intensity_offset_ok(o->inten_off, stride))
     return fail(GICP_EINVAL, "intensity offset: a multiple of 4, >= 12 and offset + 4 <= stride");
+  if (o->dk.use)
+    if (const char* e = deskew_field_error(o->dk.time_type, o->dk.time_offset_bytes, stride, o->inten_use != 0, o->inten_off))
+      return fail(GICP_EINVAL, e);
   if (dyn) {   // the keyframes come from the segmentation's static cloud: both carry the channel, or neither
     int seg_use = 0;
     if (gicp_status e = ddlo_seg_get_intensity(dyn->seg, &seg_use, nullptr)) return e;
@@ -1039,6 +1081,7 @@ static gicp_status process_scan(ddlo_odom* o, const float* xyz, size_t n, size_t
   if (st) return st;
   begin_ties(o->s2s);
   begin_ties(o->s2m);
+  o->dk_source = 0;   // (an INIT or SKIPPED frame deskews nothing and keeps a pending twist)
   std::memset(res, 0, sizeof(*res));
   copy_pose(o->T, res->T);
   copy_pose(o->T_s2s, res->T_s2s);
@@ -1075,9 +1118,13 @@ static gicp_status process_scan(ddlo_odom* o, const float* xyz, size_t n, size_t
   };
   // upload + preprocessPoints (odom.cc:442-478)
   const int N = (int)n;
-  const size_t raw = raw_bytes(n, stride, o->inten_use ? o->inten_off : 0);
+  const size_t raw = raw_bytes(n, stride, o->inten_use ? o->inten_off : 0,
+                               o->dk.use ? o->dk.time_offset_bytes + (o->dk.time_type == DDLO_TIME_F64_S ? 8 : 4) : 0);
   HIP_TRY(o->up.ensure(raw));
   HIP_TRY(hipMemcpyAsync(o->up.p, xyz, raw, hipMemcpyHostToDevice, o->s));
+  // the whole scan, before the registration pack: every reader of o->up sees the deskewed frame
+  if (o->dk.use) deskew_upload(o, N, stride);
+  else o->dk_pending = false;
   if (o->timing) o->t_phase[9] += std::chrono::duration<double>(clk::now() - t0).count();
   HIP_TRY(o->a.ensure(sizeof(float4) * n));
   // the registration scan: every point, or only the row/column filter's pixels
@@ -1155,6 +1202,7 @@ static gicp_status process_scan(ddlo_odom* o, const float* xyz, size_t n, size_t
     if (st) return st;
     metrics();
     o->have_target = true;
+    deskew_push_pose(o);
     if (dyn && dyn->map) {   // MapNode::keyframeCB receives the first keyframe as every other
       st = ddlo_map_add_odom_keyframe(dyn->map, o, (int)o->keyframes.size() - 1, nullptr);
       if (st) return st;
@@ -1195,6 +1243,7 @@ static gicp_status process_scan(ddlo_odom* o, const float* xyz, size_t n, size_t
   o->pose[1] = o->T[7];
   o->pose[2] = o->T[11];
   o->rotq = quat_from_R(o->T);
+  deskew_push_pose(o);
   if (dyn) {
     st = dynamic_step(o, *dyn, N, stride);
     if (st) return st;
@@ -1387,6 +1436,46 @@ gicp_status ddlo_odom_get_intensity(const ddlo_odom* o, int* use, size_t* offset
   if (!o) return fail(GICP_EINVAL, "null handle");
   if (use) *use = o->inten_use;
   if (offset_bytes) *offset_bytes = o->inten_off;
+  return GICP_OK;
+}
+
+gicp_status ddlo_odom_set_deskew(ddlo_odom* o, const ddlo_deskew_params* p) {
+  if (!o || !p) return fail(GICP_EINVAL, "null argument");
+  if (p->time_type < DDLO_TIME_F32_S || p->time_type > DDLO_TIME_F64_S) return fail(GICP_EINVAL, "deskew: unknown time type");
+  if (!std::isfinite(p->period) || !(p->period > 0)) return fail(GICP_EINVAL, "deskew: the period must be finite and > 0");
+  if (!std::isfinite(p->ref_time)) return fail(GICP_EINVAL, "deskew: non-finite reference time");
+  o->dk = *p;
+  o->dk.use = p->use != 0;
+  return GICP_OK;
+}
+
+gicp_status ddlo_odom_get_deskew(const ddlo_odom* o, ddlo_deskew_params* p) {
+  if (!o || !p) return fail(GICP_EINVAL, "null argument");
+  *p = o->dk;
+  return GICP_OK;
+}
+
+gicp_status ddlo_odom_set_deskew_motion(ddlo_odom* o, const double omega[3], const double t[3]) {
+  if (!o) return fail(GICP_EINVAL, "null handle");
+  if (!omega || !t) {
+    o->dk_pending = false;
+    return GICP_OK;
+  }
+  for (int a = 0; a < 3; ++a)
+    if (!std::isfinite(omega[a]) || !std::isfinite(t[a])) return fail(GICP_EINVAL, "deskew: non-finite twist");
+  std::memcpy(o->dk_pend_w, omega, sizeof(o->dk_pend_w));
+  std::memcpy(o->dk_pend_t, t, sizeof(o->dk_pend_t));
+  o->dk_pending = true;
+  return GICP_OK;
+}
+
+gicp_status ddlo_odom_deskew_motion(const ddlo_odom* o, double omega[3], double t[3], int* source) {
+  if (!o) return fail(GICP_EINVAL, "null handle");
+  for (int a = 0; a < 3; ++a) {
+    if (omega) omega[a] = o->dk_source ? o->dk_w[a] : 0.0;
+    if (t) t[a] = o->dk_source ? o->dk_t[a] : 0.0;
+  }
+  if (source) *source = o->dk_source;
   return GICP_OK;
 }
 

@@ -17,7 +17,8 @@ from .segmentation import (OBJECT_DTYPE, ClassCounts, ProjectionParams, Projecti
                            Segmentation)
 
 __all__ = ["OdomParams", "OdomResult", "DynamicParams", "NONSTATIC_FN", "Odometry", "default_odom_params",
-           "default_dynamic_params", "preprocess", "median_range", "convex_hull", "concave_hull", "TRACKED", "FIRST", "SKIPPED", "INIT"]
+           "default_dynamic_params", "preprocess", "DeskewParams", "deskew", "se3_split_log", "TIME_F32_S", "TIME_U32_NS",
+           "TIME_F64_S", "median_range", "convex_hull", "concave_hull", "TRACKED", "FIRST", "SKIPPED", "INIT"]
 
 TRACKED, FIRST, SKIPPED, INIT = 0, 1, 2, 3
 
@@ -85,6 +86,16 @@ class SortOrderStats(C.Structure):
                 ("heap_segments", C.c_int32), ("heap_longest", C.c_int32), ("threshold", C.c_int32)]
 
 
+# ddlo_time_type: the per-point time field of the deskew (include/ddlo_deskew.h)
+TIME_F32_S, TIME_U32_NS, TIME_F64_S = 0, 1, 2
+
+
+class DeskewParams(C.Structure):
+    """ddlo_deskew_params."""
+    _fields_ = [("use", C.c_int32), ("time_type", C.c_int32), ("time_offset_bytes", C.c_size_t),
+                ("ref_time", C.c_double), ("period", C.c_double)]
+
+
 _SIGS_DONE = False
 
 
@@ -127,6 +138,13 @@ def _lib():
             "ddlo_odom_get_intensity": (I, [P, C.POINTER(I), C.POINTER(S)]),
             "ddlo_odom_keyframe_points_xyzi": (I, [P, I, P, S, C.POINTER(S)]),
             "ddlo_preprocess_xyzi": (I, [I, P, S, S, S, D, D, I, P, S, C.POINTER(S)]),
+            "ddlo_odom_set_deskew": (I, [P, C.POINTER(DeskewParams)]),
+            "ddlo_odom_get_deskew": (I, [P, C.POINTER(DeskewParams)]),
+            "ddlo_odom_set_deskew_motion": (I, [P, P, P]),
+            "ddlo_odom_deskew_motion": (I, [P, P, P, C.POINTER(I)]),
+            "ddlo_se3_split_log": (I, [P, P, P]),
+            "ddlo_deskew": (I, [I, P, S, S, C.POINTER(DeskewParams), P, P, P]),
+            "ddlo_debug_deskew_time": (I, [I, P, S, S, C.POINTER(DeskewParams), P, P, I, P]),
             "ddlo_median_range": (I, [I, P, S, S, C.POINTER(C.c_float)]),
             "ddlo_convex_hull": (I, [P, I, P, I, C.POINTER(I)]),
             "ddlo_concave_hull": (I, [P, I, D, P, I, C.POINTER(I)]),
@@ -166,6 +184,29 @@ def _xyz(points) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(points, dtype=np.float32).reshape(-1, 3))
 
 
+def _records(points):
+    """Point records as (contiguous array, n, stride): (n, c) float32 rows, (n, stride) uint8 rows or a 1-D
+    structured array; x, y, z float32 first in each."""
+    a = np.asarray(points)
+    if a.dtype.names is not None and a.ndim == 1:
+        a = np.ascontiguousarray(a)
+        return a, a.shape[0], a.dtype.itemsize
+    if a.dtype == np.uint8 and a.ndim == 2:
+        a = np.ascontiguousarray(a)
+        return a, a.shape[0], a.shape[1]
+    a = np.ascontiguousarray(a, np.float32)
+    if a.ndim != 2 or a.shape[1] < 3:
+        raise ValueError("records must be (n, >=3) float32, (n, stride) uint8 or a structured array")
+    return a, a.shape[0], a.shape[1] * 4
+
+
+def _vec3(v):
+    a = np.ascontiguousarray(v, np.float64).reshape(-1)
+    if a.shape[0] != 3:
+        raise ValueError("a twist half has 3 components")
+    return a
+
+
 class Odometry:
     """OdomNode registration pipeline on one GPU."""
 
@@ -173,6 +214,7 @@ class Odometry:
         self.L = _lib()
         self.h = C.c_void_p()
         self._intensity = False     # set_intensity's flag, kept here so that process() asks nothing per frame
+        self._deskew = False        # set_deskew's, likewise
         _check(self.L.ddlo_odom_create(device, C.byref(params) if params is not None else None, C.byref(self.h)))
 
     def close(self):
@@ -226,8 +268,46 @@ class Odometry:
         _check(self.L.ddlo_odom_get_intensity(self.h, C.byref(u), C.byref(off)))
         return bool(u.value), off.value
 
+    def set_deskew(self, use, time_offset: int = 12, time_type: int = TIME_F32_S, ref_time: float = 0.0,
+                   period: float = 0.1):
+        """ddlo_odom_set_deskew (include/ddlo_deskew.h): from the next scan on, every point is moved from the
+        sensor frame at its own capture time into the sensor frame at ref_time before anything reads it.  The
+        time is the field at time_offset bytes of each record (TIME_F32_S, TIME_U32_NS or TIME_F64_S), ref_time
+        is on the same clock, period is what the twist spans.  With it on, process() takes records: (n, c)
+        float32 rows (a uint32 time viewed as float32 keeps its bits), (n, stride) uint8 rows or a structured
+        array; the dynamic entries take float32 rows.  ref_time usually changes with every scan."""
+        p = DeskewParams(int(bool(use)), int(time_type), int(time_offset), float(ref_time), float(period))
+        _check(self.L.ddlo_odom_set_deskew(self.h, C.byref(p)))
+        self._deskew = bool(use)
+
+    def deskew(self) -> DeskewParams:
+        """The setting, as a DeskewParams."""
+        p = DeskewParams()
+        _check(self.L.ddlo_odom_get_deskew(self.h, C.byref(p)))
+        return p
+
+    def set_deskew_motion(self, omega=None, t=None):
+        """ddlo_odom_set_deskew_motion: the caller's twist (rotation vector rad, translation m, over one period,
+        in the frame of the reference instant) for the next scan that is uploaded, and for that scan only;
+        None clears a pending one.  Without one, a deskewing driver predicts from its last two poses."""
+        if omega is None or t is None:
+            _check(self.L.ddlo_odom_set_deskew_motion(self.h, None, None))
+            return
+        w, v = _vec3(omega), _vec3(t)
+        _check(self.L.ddlo_odom_set_deskew_motion(self.h, _ptr(w), _ptr(v)))
+
+    def deskew_motion(self):
+        """(omega, t, source) applied to the last scan: source 0 none, 1 predicted, 2 the caller's."""
+        w, v, src = np.zeros(3), np.zeros(3), C.c_int()
+        _check(self.L.ddlo_odom_deskew_motion(self.h, _ptr(w), _ptr(v), C.byref(src)))
+        return w, v, src.value
+
     def process(self, points) -> OdomResult:
         r = OdomResult()
+        if self._deskew:
+            a, n, stride = _records(points)
+            _check(self.L.ddlo_odom_process(self.h, _ptr(a) if n else None, n, stride, C.byref(r)))
+            return r
         if self._intensity:
             a = np.ascontiguousarray(points, np.float32)
             if a.ndim != 2 or a.shape[1] < 4:
@@ -397,6 +477,39 @@ def preprocess(points, crop_size: float = 0.0, leaf: float = 0.0, device: int = 
         _check(_lib().ddlo_preprocess_ordered(device, _ptr(a), a.shape[0], 12, float(crop_size), float(leaf),
                                               int(order), _ptr(out), out.shape[0], C.byref(n)))
     return out[:n.value]
+
+
+def deskew(records, omega, t, time_offset: int, time_type: int = TIME_F32_S, ref_time: float = 0.0,
+           period: float = 0.1, device: int = 0) -> np.ndarray:
+    """ddlo_deskew: the deskew pass on its own.  records as Odometry.set_deskew describes them; returns the
+    (n, 3) float32 points in the sensor frame at ref_time."""
+    a, n, stride = _records(records)
+    p = DeskewParams(1, int(time_type), int(time_offset), float(ref_time), float(period))
+    w, v = _vec3(omega), _vec3(t)
+    out = np.zeros((max(n, 1), 3), np.float32)
+    _check(_lib().ddlo_deskew(device, _ptr(a) if n else None, n, stride, C.byref(p), _ptr(w), _ptr(v), _ptr(out)))
+    return out[:n]
+
+
+def deskew_time(records, omega, t, time_offset: int, time_type: int = TIME_F32_S, ref_time: float = 0.0,
+                period: float = 0.1, reps: int = 100, device: int = 0) -> np.ndarray:
+    """ddlo_debug_deskew_time: the device time of the deskew pass alone in milliseconds, reps times, each behind
+    a fresh upload of the records."""
+    a, n, stride = _records(records)
+    p = DeskewParams(1, int(time_type), int(time_offset), float(ref_time), float(period))
+    w, v = _vec3(omega), _vec3(t)
+    ms = np.zeros(int(reps), np.float32)
+    _check(_lib().ddlo_debug_deskew_time(device, _ptr(a), n, stride, C.byref(p), _ptr(w), _ptr(v), int(reps), _ptr(ms)))
+    return ms
+
+
+def se3_split_log(T):
+    """ddlo_se3_split_log: (omega, t) of a 4x4 transform taken as float32: the rotation vector of its 3x3 block
+    and its translation column."""
+    a = np.ascontiguousarray(T, np.float32).reshape(16)
+    w, v = np.zeros(3), np.zeros(3)
+    _check(_lib().ddlo_se3_split_log(_ptr(a), _ptr(w), _ptr(v)))
+    return w, v
 
 
 def preprocess_downsampled(points, rows: int, cols: int, row_step: int, col_step: int, crop_size: float = 0.0,

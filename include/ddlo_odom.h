@@ -293,5 +293,7 @@ gicp_status ddlo_concave_hull(const float* xyz, int n, double alpha, int32_t* id
 
 /* the opt-in intensity channel: ddlo_odom_set_intensity, ddlo_odom_keyframe_points_xyzi, ddlo_preprocess_xyzi */
 #include "ddlo_intensity.h"
+/* the opt-in motion deskew: ddlo_odom_set_deskew, ddlo_odom_set_deskew_motion, ddlo_deskew, ddlo_se3_split_log */
+#include "ddlo_deskew.h"
 
 #endif /* DDLO_ODOM_H */
